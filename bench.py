@@ -10,6 +10,11 @@ Inputs (frames, CAD models, cached spectral operators) are resident in HBM befor
   python bench.py [--gpus N --steps K --warmup W --batch B]   (N > 1: spawns N ranks itself)
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 Rank 0 prints one JSON line (contract in the task statement / DESIGN.md §Measurement).
+
+A plain run sets up, warms up, times the K steps and prints the headline line. --full adds
+what takes runs of its own after the timed region: the per-kernel probe steps and their
+rooflines, the roofline probes, the CPU baseline and the pose-vs-reference checks.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -52,10 +57,17 @@ def parse():
                     help="train / infer at the reference's real sizes: ragged crops of ~200-2000 points (the "
                          "object.py:145-148 sample policy), ~5000-vertex CADs, collate padding to 2000")
     ap.add_argument("--cad-points", type=int, default=5000, help="--ragged: CAD vertices")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel probe steps (kernels / roofline keys), the "
+                         "roofline probes, the CPU baseline and the pose-vs-reference checks (each still has its "
+                         "own --no-* / --probe-steps switch); off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (train: also the updated weights) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-crops", type=int, default=30, help="bounded CPU-baseline sample (crops)")
     ap.add_argument("--pose-crops", type=int, default=8,
-                    help="train: crops of the post-timing pose-vs-reference check (0: skip)")
+                    help="train, --full: crops of the post-timing pose-vs-reference check (0: skip)")
     ap.add_argument("--no-roofline-probe", action="store_true")
     ap.add_argument("--eager", action="store_true", help="no HIP graph: launch every kernel from Python")
     ap.add_argument("--side-after", action="store_true",
@@ -75,7 +87,7 @@ def parse():
                     help="infer: 3 = also overlap the pose stage of batch i-1 with the model of batch i")
     ap.add_argument("--no-overlap", action="store_true",
                     help="graph mode without overlapping crop formation of the next batch")
-    ap.add_argument("--probe-steps", type=int, default=2, help="eager steps after timing for the kernel breakdown")
+    ap.add_argument("--probe-steps", type=int, default=2, help="--full: eager steps after timing for the kernel breakdown")
     ap.add_argument("--mode", choices=("train", "infer", "corr4096", "icp", "teaser", "operators", "ransac_ref"),
                     default="train",
                     help="train: the headline fwd+bwd step (default); infer: configs[1]/[3] inference; "
@@ -521,6 +533,56 @@ def setup_dist(gpus: int = 0):
 
 
 POSE_CHECK = {}  # mode -> the post-timing pose-vs-reference check (cpu_baseline leg)
+DUMP_EXTRA = {}  # "fn": () -> {name: tensor}, state the timed step updates beside the log it returns (train: weights)
+DUMP_BUDGET = 60_000_000  # --dump-outputs: array bytes in all (under 64 MB with the .npy headers)
+
+
+def flatten_outputs(obj, prefix: str = "") -> dict:
+    """The tensors / arrays / numbers a step returned (nested dicts, lists) as {name: ndarray},
+    float64 for float64 and integer values, float32 for every other float and for bools."""
+    out = {}
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            out.update(flatten_outputs(v, f"{prefix}_{k}" if prefix else str(k)))
+        return out
+    if isinstance(obj, (list, tuple)) and any(isinstance(v, (torch.Tensor, np.ndarray, dict)) for v in obj):
+        for i, v in enumerate(obj):
+            out.update(flatten_outputs(v, f"{prefix}_{i}" if prefix else str(i)))
+        return out
+    if isinstance(obj, torch.Tensor):
+        t = obj.detach()
+        t = t.to(torch.float64) if (t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)) \
+            else t.to(torch.float32)
+        out[prefix or "out"] = t.cpu().numpy()
+    elif isinstance(obj, (np.ndarray, np.generic, bool, int, float, list, tuple)):
+        try:
+            a = np.asarray(obj)
+        except ValueError:
+            return out
+        if a.dtype.kind in "iu" or a.dtype == np.float64:
+            out[prefix or "out"] = a.astype(np.float64)
+        elif a.dtype.kind in "fb":
+            out[prefix or "out"] = a.astype(np.float32)
+    return out
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """Write {name: ndarray} as path/<name>.npy. Over DUMP_BUDGET bytes in all, every array above
+    an equal share keeps a fixed sample: the elements at sorted indices drawn with seed 0 (the
+    same indices for the same shapes, so two builds' files compare element for element)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(arrays))
+    over = sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if over and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        safe = "".join(c if (c.isalnum() or c in "._-") else "_" for c in name)
+        np.save(os.path.join(path, safe + ".npy"), a)
+        written[safe] = list(a.shape)
+    return written
 
 
 def ragged_setup(B: int, n1: int, rank: int, dev):
@@ -613,6 +675,8 @@ def build_train(args, dev, rank, world):
         torch.cuda.synchronize()
         return cpu_pose_check(model, fb, op, crops, out, n_sample, 1024, 5)
     POSE_CHECK["fn"] = pose_check
+    # a training step's result is the updated model: every parameter, in model.parameters() order
+    DUMP_EXTRA["fn"] = lambda: {"params": torch.cat([p.detach().reshape(-1) for p in model.parameters()])}
     return one_step, probe, TRAIN_METRIC, B, config
 
 
@@ -1030,6 +1094,12 @@ def main():
     if hasattr(one_step, "flush"):  # PipelinedTrainer: the last step's IR (computed beside the next step)
         one_step.flush()
         torch.cuda.synchronize()
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything below runs the step again
+        arrays = flatten_outputs(log)
+        if "fn" in DUMP_EXTRA:
+            arrays.update(flatten_outputs(DUMP_EXTRA["fn"]()))
+        dumped = dump_outputs(args.dump_outputs, arrays)
     extra = {}
     # index consumers' per-crop status (IR / RANSAC met an out-of-range index; 0 expected), read
     # after timing like pair_overflow
@@ -1054,7 +1124,7 @@ def main():
                          "mean_updates": round(float(st[:, 2].mean()), 2), "max_updates": int(st[:, 2].max()),
                          "converged": int(st[:, 3].sum())}}
     probe_steps = args.steps
-    if not args.eager:
+    if args.full and not args.eager:
         # per-kernel HIP events cannot sit inside a graph: time the same step eagerly, on
         # the same resident inputs, right after the timed region (not part of `value`)
         # A device-side sleep heads each probe step so the host enqueues the whole step
@@ -1099,16 +1169,21 @@ def main():
             "dtype": "bf16" if (args.mode == "corr4096" and args.fd_precision != "fp32") else "fp32",
             "data": "synthetic (seeded ellipsoid RGB-D frames, random-init DPFM)",
             "config": config,
-            "roofline": roof,
-            "roofline_crop_formation": (dict(roofline_for(dom_crop[0], dom_crop[1]),
-                                             stream="side (overlapped with the main step)")
-                                        if dom_crop is not None and overlapped else
-                                        (roofline_for(dom_crop[0], dom_crop[1]) if dom_crop else None)),
-            "roofline_mfma_kernels": {k: {"achieved": v["achieved"], "frac": v["frac"], "unit": v["unit"]}
-                                      for k, v in mfma_fams.items()},
-            "kernels": kernels,
         }
+        if args.full or args.eager:  # the per-kernel probe ran (--eager: inside the timed steps)
+            out.update({
+                "roofline": roof,
+                "roofline_crop_formation": (dict(roofline_for(dom_crop[0], dom_crop[1]),
+                                                 stream="side (overlapped with the main step)")
+                                            if dom_crop is not None and overlapped else
+                                            (roofline_for(dom_crop[0], dom_crop[1]) if dom_crop else None)),
+                "roofline_mfma_kernels": {k: {"achieved": v["achieved"], "frac": v["frac"], "unit": v["unit"]}
+                                          for k, v in mfma_fams.items()},
+                "kernels": kernels,
+            })
         out.update(extra)
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if "pk_ransac" in kern and args.mode in ("infer", "corr4096", "ransac_ref"):
             rk = kern["pk_ransac"]
             crops_per_launch = 1 if args.mode == "corr4096" else units
@@ -1119,14 +1194,14 @@ def main():
                              "ms_per_launch": round(rk["avg_ms"], 4), "hypotheses_per_launch":
                              args.hypotheses * crops_per_launch, "valu64_achieved_tflops": r64["achieved"],
                              "valu64_frac": r64["frac"]}
-        if args.mode == "train" and not args.no_roofline_probe and world == 1:
+        if args.full and args.mode == "train" and not args.no_roofline_probe and world == 1:
             out["roofline_ball_query"] = ball_query_roofline(dev)
             out["roofline_feat_dist"] = feat_dist_roofline(dev)
-        if args.mode == "infer" and not args.no_roofline_probe and world == 1 and args.points == 1024:
+        if args.full and args.mode == "infer" and not args.no_roofline_probe and world == 1 and args.points == 1024:
             # the configured solver's top-5 timed as the pipeline issues it (graph replays, warm
             # clocks); roofline_mfma_kernels' entry is the eager per-op probe (host gaps included)
             out["roofline_feat_dist_top5"] = feat_dist_roofline(dev, topk=5)
-        if not args.no_cpu_baseline and world == 1 and not args.ragged:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.ragged:
             if args.mode == "train":
                 out["cpu_baseline"] = cpu_baseline(args.cpu_crops, args.points, args.points)
                 if args.pose_crops > 0:

@@ -69,6 +69,48 @@ def test_global_batch_divides_over_ranks():
         b.apply_global_batch(argparse.Namespace(global_batch=30, batch=32), 4)
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """--full (probe steps, roofline probes, CPU baseline, pose checks) and --dump-outputs are off
+    unless asked for; the older switches stay accepted beside them."""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d", "--no-cpu-baseline",
+                                      "--no-roofline-probe", "--probe-steps", "0"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "d" and a.no_cpu_baseline and a.probe_steps == 0
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: every tensor / array / number of the step's (nested) result becomes one
+    float32 / float64 .npy; over the byte budget the large arrays keep the same seeded sample
+    from call to call."""
+    import numpy as np
+    import torch
+    b = _bench()
+    log = {"loss": torch.tensor(1.5), "idx": torch.arange(6, dtype=torch.int32).reshape(2, 3),
+           "flag": torch.tensor(True), "T": torch.eye(4, dtype=torch.float64), "h": torch.ones(3, dtype=torch.bfloat16),
+           "nested": {"residual": 0.25, "iterations": 3, "info": np.arange(4, dtype=np.int64)}, "name": "x"}
+    arrays = b.flatten_outputs(log)
+    assert set(arrays) == {"loss", "idx", "flag", "T", "h", "nested_residual", "nested_iterations", "nested_info"}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert arrays["idx"].dtype == np.float64 and arrays["T"].dtype == np.float64 and arrays["h"].dtype == np.float32
+    assert np.array_equal(arrays["idx"], np.arange(6.0).reshape(2, 3)) and arrays["flag"] == 1.0
+    shapes = b.dump_outputs(str(tmp_path / "a"), arrays)
+    assert shapes["idx"] == [2, 3] and sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in arrays)
+    assert np.array_equal(np.load(tmp_path / "a" / "T.npy"), np.eye(4))
+    # over budget: the small array whole, the large one sampled, identically in two calls
+    monkeypatch.setattr(b, "DUMP_BUDGET", 4096)
+    big = {"small": np.arange(8, dtype=np.float32), "big": np.arange(10000, dtype=np.float64)}
+    b.dump_outputs(str(tmp_path / "b"), big)
+    b.dump_outputs(str(tmp_path / "c"), big)
+    s1, s2 = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+    assert np.array_equal(np.load(tmp_path / "b" / "small.npy"), big["small"])
+    assert np.array_equal(s1, s2) and s1.size == 256 and np.all(np.diff(s1) > 0)
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 4096 + 2 * 128
+
+
 def test_gloo_world2_train_config(tmp_path):
     """At world size 2 (gloo, CPU) the config dict the training line would print: configs[2] by name
     with --global-batch 32, per-rank B = 16, parallelism dp2."""

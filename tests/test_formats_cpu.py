@@ -5,8 +5,7 @@
     masks), read back by BopScenes: arrays and JSON entries identical; mapping_list with the
     reference's visib / obj_take filters; object frames -> the oracle crop identical to the one
     built from the golden arrays directly.
-  * PLY: ASCII (VCGLIB-style, faces + extra vertex properties) and binary round trips; the
-    reference's own models/obj_000001.ply when /root/reference is present (CPU suite only).
+  * PLY: ASCII (VCGLIB-style, faces + extra vertex properties) and binary round trips.
   * operator caches: sparse COO L / gradX / gradY as *_idx / *_val, allow_pickle=False, object
     entries refused (not unpickled).
   * result bundles: eval.py's (CAD, PC, Obj) tuple through torch.load(weights_only=True) and
@@ -114,17 +113,6 @@ def test_ply_ascii_and_binary(tmp_path):
     np.testing.assert_array_equal(a.vertices, v32.astype(np.float64))
     np.testing.assert_array_equal(a.faces, f)
     assert a.properties["red"][0] == 255
-
-
-@pytest.mark.skipif(not os.path.exists("/root/reference/sample-data/lm/models/obj_000001.ply"),
-                    reason="reference sample data absent")
-def test_ply_reads_reference_model():
-    p = FMT.read_ply("/root/reference/sample-data/lm/models/obj_000001.ply")
-    assert p.vertices.shape == (5841, 3) and p.faces.shape == (11678, 3)
-    assert p.faces.min() >= 0 and p.faces.max() < 5841
-    info = FMT.load_models_info("/root/reference/sample-data/lm/models")
-    d = np.sqrt(((p.vertices[:, None, :] - p.vertices[None, ::7, :]) ** 2).sum(-1)).max()
-    assert d <= info["1"]["diameter"] * (1 + 1e-3)
 
 
 def test_operator_cache_round_trip_and_pickle_refusal(tmp_path):

@@ -7,12 +7,12 @@ export TMPDIR=/tmp
 O=gpurun_out/${TAG:-close}
 mkdir -p $O
 step() { local name=$1 to=$2; shift 2; timeout -k 10 $to "$@" > $O/$name.out 2> $O/$name.err || { echo "$name failed"; tail -20 $O/$name.err; exit 1; }; tail -c 400 $O/$name.out; echo; }
-step train 600 python3 -u bench.py
-step infer 300 python3 -u bench.py --mode infer
-step infer2048 300 python3 -u bench.py --mode infer --points 2048 --no-cpu-baseline
-step ragged 600 python3 -u bench.py --ragged --no-cpu-baseline
-[ -n "$SKIP_OPS" ] || step ops 400 python3 -u bench.py --mode operators --batch 8 --steps 3 --warmup 1
-step prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline-probe
+step train 600 python3 -u bench.py --full
+step infer 300 python3 -u bench.py --full --mode infer
+step infer2048 300 python3 -u bench.py --full --mode infer --points 2048 --no-cpu-baseline
+step ragged 600 python3 -u bench.py --full --ragged --no-cpu-baseline
+[ -n "$SKIP_OPS" ] || step ops 400 python3 -u bench.py --full --mode operators --batch 8 --steps 3 --warmup 1
+step prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-roofline-probe
 find $O/prof -type f ! -name "*stats.csv" -delete
 # the timed steps alone (no eager warm-up / probe steps in the window): tools/step_window_summary.py
 step steptrace 400 rocprofv3 --kernel-trace --output-format csv -d $O/steptrace -o run -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-roofline-probe --probe-steps 0

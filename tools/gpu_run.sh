@@ -19,18 +19,18 @@ run() {  # name timeout cmd...
 }
 for step in "$@"; do
   case $step in
-    icp) run icp 200 python bench.py --mode icp ;;
-    teaser) run teaser 200 python bench.py --mode teaser --steps 5 --warmup 1 ;;
-    ops) run ops 300 python bench.py --mode operators --batch 8 --steps 3 --warmup 1 ;;
-    infer) run infer 300 python bench.py --mode infer ;;
-    corr) run corr 300 python bench.py --mode corr4096 ;;
+    icp) run icp 200 python bench.py --full --mode icp ;;
+    teaser) run teaser 200 python bench.py --full --mode teaser --steps 5 --warmup 1 ;;
+    ops) run ops 300 python bench.py --full --mode operators --batch 8 --steps 3 --warmup 1 ;;
+    infer) run infer 300 python bench.py --full --mode infer ;;
+    corr) run corr 300 python bench.py --full --mode corr4096 ;;
     tests) run tests 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;;
     testsall) run testsall 1000 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py ;;
-    benchq) run benchq 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench) run bench 600 python bench.py --full ;;
+    benchq) run benchq 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline ;;
     benche) run benche 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline-probe --eager ;;
-    prof) run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -o run -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline-probe
+    prof) run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -o run -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-roofline-probe
           find "$out/prof" -type f ! -name "*stats.csv" -delete ;;
     kbench) run kbench 300 python tools/kbench.py ;;
     steptrace) run steptrace_bench 400 rocprofv3 --kernel-trace --output-format csv -d "$out/steptrace" -o run -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-roofline-probe --probe-steps 0
@@ -51,11 +51,11 @@ for step in "$@"; do
     pmcstep) TAG=$tag/pmcstep run pmcstep 700 bash tools/pmc_step.sh ;;
     kprof) run kprof 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kprof" -o run -- python tools/kbench.py
           find "$out/kprof" -type f ! -name "*stats.csv" -delete ;;
-    pmcm) run pmcm 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$out/pmcm" -o run -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --eager --probe-steps 1
+    pmcm) run pmcm 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$out/pmcm" -o run -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --eager --probe-steps 1
           python tools/mfma_util.py "$out/pmcm" fd_main_kernel attn_fwd attn_bwd wgrad_grouped_kernel linear_fwd_rows linear_fwd_cf nce_pass > "$out/mfma_util_step.json" 2>&1
           find "$out/pmcm" -type f -name "*.csv" -size +2M -delete ;;
-    pmc) run pmcf 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$out/pmcf" -o run -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --eager --probe-steps 1
-         run pmcw 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$out/pmcw" -o run -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --eager --probe-steps 1
+    pmc) run pmcf 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$out/pmcf" -o run -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --eager --probe-steps 1
+         run pmcw 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$out/pmcw" -o run -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --eager --probe-steps 1
          python tools/pmc_summary.py "$out/pmcf" "$out/pmcw" "$out/pmc_traffic.json" > "$out/pmc_summary.log" 2>&1
          find "$out/pmcf" "$out/pmcw" -type f -name "*.csv" -size +2M -delete ;;
     fdb) run fdb 300 python tools/fd_bench.py ;;
