@@ -80,35 +80,58 @@ __device__ __forceinline__ int swz(int c) { return ((c + 4) >> 3) & 1; }
 // quad is one conflict-free ds_read_b128 (8 per lane per tile).
 constexpr int kFQ = 128;                            // queries per forward block
 constexpr int kFKV = kT * kSA + kD * kSQ;           // floats per K / V tile buffer
+//
+// VARLEN (masked mode, pk_attention_fwd_varlen): crop b has qlen[b] real queries and klen[b] real
+// keys (null: all). N and M stay the addressing strides; Ne / Me (block-uniform, read on the device)
+// replace them in every bound, so the key-tile loop ends at Me with the same full / ragged tile
+// sequence an unpadded call of that crop alone runs. Rows n >= Ne of out and lse are written as 0;
+// a block wholly past Ne, or a crop without keys, writes its zeros and does no tile work. The
+// !VARLEN instantiation has Ne = N, Me = M folded: the code it was before the switch.
+template <bool VARLEN>
 __global__ __launch_bounds__(512) void attn_fwd_kernel(const float* __restrict__ q,
                                                        const float* __restrict__ k,
                                                        const float* __restrict__ v, int H, int N,
                                                        int M, int64_t sbk, int64_t sbv, float* __restrict__ out,
-                                                       float* __restrict__ lse) {
+                                                       float* __restrict__ lse, const int* __restrict__ qlen,
+                                                       const int* __restrict__ klen) {
   __shared__ __attribute__((aligned(16))) float KV[2 * kFKV];
   const int3 lb = pk::xcd_block3();  // a (crop, head)'s query blocks share one XCD's L2 (K / V)
   const int h = lb.y, b = lb.z;
   const int lane = pk::lane_id(), g = lane >> 4, c = lane & 15;
   const int qi = lb.x * kFQ + pk::wave_id() * 16 + c;
+  int Ne = N, Me = M;
+  if constexpr (VARLEN) {
+    if (qlen) Ne = min(max(qlen[b], 0), N);
+    if (klen) Me = min(max(klen[b], 0), M);
+    if (lb.x * kFQ >= Ne || Me == 0) {  // block-uniform: no query or no key of this block is real
+      if (qi < N) {
+        float* ob = out + ((int64_t)b * kD * H + h) * N;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ob[(int64_t)(4 * g + r) * H * N + qi] = 0.f;
+        if (g == 0) reinterpret_cast<float2*>(lse)[((int64_t)b * H + h) * N + qi] = make_float2(0.f, 0.f);
+      }
+      return;
+    }
+  }
   const float* qb = q + ((int64_t)b * kD * H + h) * N;
   const float* kb = k + (int64_t)b * sbk + (int64_t)h * M;
   const float* vb = v + (int64_t)b * sbv + (int64_t)h * M;
   const int HM = H * M;
   float qr[4];
 #pragma unroll
-  for (int s = 0; s < 4; ++s) qr[s] = qi < N ? qb[(int64_t)(4 * s + g) * H * N + qi] * kScale : 0.f;
+  for (int s = 0; s < 4; ++s) qr[s] = qi < Ne ? qb[(int64_t)(4 * s + g) * H * N + qi] * kScale : 0.f;
   // staging: threads 0-255 carry K, 256-511 V; thread -> (key sk = (tid & 255) >> 2, d 4 sp .. + 3)
   const int sk = (threadIdx.x & 255) >> 2, sp = threadIdx.x & 3;
   const bool stage_k = threadIdx.x < 256;
   const float* src = stage_k ? kb : vb;
   float pf[4];
   auto issue = [&](int k0) {
-    const int kk = k0 + sk, kc = kk < M ? kk : 0;
+    const int kk = k0 + sk, kc = kk < Me ? kk : 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) pf[i] = src[(int64_t)(4 * sp + i) * HM + kc];
   };
   auto stage = [&](int k0, float* buf) {
-    const bool ok = k0 + sk < M;
+    const bool ok = k0 + sk < Me;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const float x = ok ? pf[i] : 0.f;
@@ -125,7 +148,7 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const float* __restrict__
   float m = -__builtin_huge_valf(), l = 0.f;
   issue(0);
   stage(0, KV);
-  if (kT < M) issue(kT);
+  if (kT < Me) issue(kT);
   const int gs = 4 * (g ^ swz(c));
   // one 64-key tile; RAG: the ragged last tile (keys past M masked to -inf) — a separate
   // instantiation, so the full tiles carry no masking code (a uniform branch the compiler would
@@ -145,7 +168,7 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const float* __restrict__
       for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (k0 + 16 * t + 4 * g + r >= M) st[t][r] = -__builtin_huge_valf();
+          if (k0 + 16 * t + 4 * g + r >= Me) st[t][r] = -__builtin_huge_valf();
     }
     float mt = -__builtin_huge_valf();
 #pragma unroll
@@ -191,24 +214,24 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const float* __restrict__
   auto sync_stage = [&](int j) {
     const int k0 = j * kT;
     __syncthreads();  // tile j staged; the buffer of tile j - 1 free
-    if (k0 + kT < M) {
+    if (k0 + kT < Me) {
       stage(k0 + kT, KV + ((j + 1) & 1) * kFKV);
-      if (k0 + 2 * kT < M) issue(k0 + 2 * kT);
+      if (k0 + 2 * kT < Me) issue(k0 + 2 * kT);
     }
   };
-  const int nfull = M / kT;
+  const int nfull = Me / kT;
   int j = 0;
   for (; j < nfull; ++j) {
     sync_stage(j);
     tile(KV + (j & 1) * kFKV, j * kT, std::false_type{});
   }
-  if (j * kT < M) {  // the ragged last tile
+  if (j * kT < Me) {  // the ragged last tile
     sync_stage(j);
     tile(KV + (j & 1) * kFKV, j * kT, std::true_type{});
   }
   l = grp_sum(l);
   const f32x4 accs = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-  if (qi < N) {
+  if (qi < Ne) {
     const float inv = 1.f / l;
     float* ob = out + ((int64_t)b * kD * H + h) * N;
 #pragma unroll
@@ -217,6 +240,11 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const float* __restrict__
       float2* ms = reinterpret_cast<float2*>(lse) + ((int64_t)b * H + h) * N + qi;
       *ms = make_float2(m, inv);
     }
+  } else if (VARLEN && qi < N) {  // padded queries of a live block
+    float* ob = out + ((int64_t)b * kD * H + h) * N;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ob[(int64_t)(4 * g + r) * H * N + qi] = 0.f;
+    if (g == 0) reinterpret_cast<float2*>(lse)[((int64_t)b * H + h) * N + qi] = make_float2(0.f, 0.f);
   }
 }
 
@@ -235,11 +263,19 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const float* __restrict__
 // delta = rowsum(dO * O) is formed per query as the tile is staged (fmaf over d in order, the
 // four lanes' partial sums of a query added as (p0 + p1) + (p2 + p3)).
 
+//
+// VARLEN (pk_attention_bwd_varlen): Ne = qlen[b] bounds the query-tile loop, Me = klen[b] the keys
+// (N, M stay the strides). A key block wholly past Me, or a crop without queries, writes zeros to
+// its dk / dv rows and returns: it writes no dQ partial, and attn_bwd_dq_reduce_varlen_kernel adds
+// only the slots of live key blocks, only for rows < Ne, and writes 0 elsewhere — so the result
+// never depends on what the work buffer held. Keys in [Me, M) of a live block get dk = dv = 0.
+template <bool VARLEN>
 __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
     const float* __restrict__ o, const float* __restrict__ dout, const float* __restrict__ lse, int H, int N,
     int M, int64_t sbk, int64_t sbv, int64_t sbdk, int64_t sbdv, float* __restrict__ dq,
-    float* __restrict__ part, float* __restrict__ dk, float* __restrict__ dv) {
+    float* __restrict__ part, float* __restrict__ dk, float* __restrict__ dv, const int* __restrict__ qlen,
+    const int* __restrict__ klen) {
   // two query-tile buffers, each: Q [q][p(d)] (p(4 s + g) = 4 g + s), dO [q][p(d)], Q [d][q],
   // dO [d][q], then (m, 1 / sum, delta) per query; two dQ-partial buffers [wave][q][d]; the per-wave
   // dS transpose tiles. One barrier per query tile: tile j + 1 is staged and tile j - 1's partials
@@ -255,6 +291,26 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(
   const float2* lb = reinterpret_cast<const float2*>(lse) + ((int64_t)b * H + h) * N;
   // this wave's keys: kk(t) = kb0 + 16 t + c (S / dP operands), kk(t, r) = kb0 + 16 t + 4 g + r (K^T)
   const int kb0 = kblk * kKB + 32 * wave;
+  int Ne = N, Me = M;
+  if constexpr (VARLEN) {
+    if (qlen) Ne = min(max(qlen[b], 0), N);
+    if (klen) Me = min(max(klen[b], 0), M);
+    if (kblk * kKB >= Me || Ne == 0) {  // block-uniform: nothing to contract
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int kj = kb0 + 16 * t + c;
+        if (kj < M) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int64_t a = (int64_t)h * M + (int64_t)(4 * g + r) * H * M + kj;
+            dk[(int64_t)b * sbdk + a] = 0.f;
+            dv[(int64_t)b * sbdv + a] = 0.f;
+          }
+        }
+      }
+      return;
+    }
+  }
   const float* kbp = k + (int64_t)b * sbk + (int64_t)h * M;
   const float* vbp = v + (int64_t)b * sbv + (int64_t)h * M;
   float kr[2][4], vr[2][4], kt[2][4];
@@ -263,16 +319,16 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(
     const int kj = kb0 + 16 * t + c;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const int64_t a = (int64_t)(4 * s + g) * H * M + (kj < M ? kj : 0);
+      const int64_t a = (int64_t)(4 * s + g) * H * M + (kj < Me ? kj : 0);
       const float kv = kbp[a], vv = vbp[a];  // unconditional at a clamped key
-      kr[t][s] = kj < M ? kv * kScale : 0.f;
-      vr[t][s] = kj < M ? vv : 0.f;
+      kr[t][s] = kj < Me ? kv * kScale : 0.f;
+      vr[t][s] = kj < Me ? vv : 0.f;
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int kj2 = kb0 + 16 * t + 4 * g + r;
-      const float kv = kbp[(int64_t)c * H * M + (kj2 < M ? kj2 : 0)];
-      kt[t][r] = kj2 < M ? kv : 0.f;
+      const float kv = kbp[(int64_t)c * H * M + (kj2 < Me ? kj2 : 0)];
+      kt[t][r] = kj2 < Me ? kv : 0.f;
     }
   }
   // keys past M: S starts at -inf (the MFMA chain's initial accumulator), so P = exp2(-inf) = 0 and
@@ -280,7 +336,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(
   f32x4 s0[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    const float z = kb0 + 16 * t + c < M ? 0.f : -__builtin_huge_valf();
+    const float z = kb0 + 16 * t + c < Me ? 0.f : -__builtin_huge_valf();
     s0[t] = f32x4{z, z, z, z};
   }
   // staging: waves 0-3 carry dO and O (and form delta), waves 4-7 Q and (m, 1 / sum); thread ->
@@ -290,7 +346,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(
   float pf[8];
   float2 pm = make_float2(0.f, 0.f);
   auto issue = [&](int q0) {
-    const int qq = q0 + sq, qc = qq < N ? qq : 0;
+    const int qq = q0 + sq, qc = qq < Ne ? qq : 0;
     const float* src0 = stage_g ? dout : q;
 #pragma unroll
     for (int i = 0; i < 4; ++i) pf[i] = src0[qoff + (int64_t)(4 * sp + i) * HN + qc];
@@ -302,7 +358,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(
     }
   };
   auto stage = [&](int q0, float* tb) {
-    const bool ok = q0 + sq < N;
+    const bool ok = q0 + sq < Ne;
     float* A = tb + (stage_g ? kOG : kOA);
     float* T = tb + (stage_g ? kOGT : kOQT);
     float* MI = tb + kOMI;
@@ -333,7 +389,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(
   float* ts = TS + wave * 16 * kSTs;
   const int P = gridDim.x;
   float* dst = kblk == 0 ? dq : part + (int64_t)(kblk - 1) * ((int64_t)gridDim.z * kD * HN);
-  const float osc = P == 1 ? kScale : 1.f;  // one key block: dq final here
+  const float osc = !VARLEN && P == 1 ? kScale : 1.f;  // one key block: dq final here (VARLEN: always reduced)
   // the 8 waves' partials of tile q0 (buffer rb) added in wave order: waves 0-3, thread = (query qq,
   // channels 4 j .. 4 j + 3), conflict-free ds_read_b128 rows
   auto reduce = [&](int q0, const float* rb) {
@@ -342,7 +398,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(
       f32x4 sum = *reinterpret_cast<const f32x4*>(&rb[qq * kSRq + 4 * j]);
 #pragma unroll
       for (int w = 1; w < 8; ++w) sum += *reinterpret_cast<const f32x4*>(&rb[w * kT * kSRq + qq * kSRq + 4 * j]);
-      if (q0 + qq < N) {
+      if (q0 + qq < Ne) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) dst[qoff + (int64_t)(4 * j + i) * HN + q0 + qq] = sum[i] * osc;
       }
@@ -350,16 +406,16 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(
   };
   issue(0);
   stage(0, TB);
-  if (kT < N) issue(kT);
+  if (kT < Ne) issue(kT);
   int j = 0;
   for (;; ++j) {
     const int q0 = j * kT;
     const float* tb = TB + (j & 1) * kTileF;
     __syncthreads();  // tile j staged; tile j - 1's partials complete; buffers of tile j - 1 free
     if (j > 0) reduce(q0 - kT, RQ + ((j - 1) & 1) * 8 * kT * kSRq);
-    if (q0 + kT < N) {
+    if (q0 + kT < Ne) {
       stage(q0 + kT, TB + ((j + 1) & 1) * kTileF);
-      if (q0 + 2 * kT < N) issue(q0 + 2 * kT);
+      if (q0 + 2 * kT < Ne) issue(q0 + 2 * kT);
     }
     const float* QA = tb + kOA;
     const float* GA = tb + kOG;
@@ -417,7 +473,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) *reinterpret_cast<f32x4*>(&rq[(16 * u + c) * kSRq + 4 * g]) = dqa[u];
-    if (q0 + kT >= N) break;
+    if (q0 + kT >= Ne) break;
   }
   __syncthreads();
   reduce(j * kT, RQ + (j & 1) * 8 * kT * kSRq);
@@ -426,11 +482,12 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(
     const int kj = kb0 + 16 * t + c;
     if (kj < M) {
       const f32x4 dks = dka[t][0] + dka[t][1], dvs = dva[t][0] + dva[t][1];
+      const bool real = !VARLEN || kj < Me;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t a = (int64_t)h * M + (int64_t)(4 * g + r) * H * M + kj;
-        dk[(int64_t)b * sbdk + a] = dks[r] * kScale;
-        dv[(int64_t)b * sbdv + a] = dvs[r];
+        dk[(int64_t)b * sbdk + a] = real ? dks[r] * kScale : 0.f;
+        dv[(int64_t)b * sbdv + a] = real ? dvs[r] : 0.f;
       }
     }
   }
@@ -448,6 +505,29 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_reduce_kernel(float* __restri
   }
 }
 
+// the length-aware form: one thread per element of dq [B, kD * H, N]. Crop b adds the slots of its
+// live key blocks (p < ceil(klen[b] / kKB)) in slot order for rows n < qlen[b] — the same sum and
+// scale as above — and writes 0 to every other element; slots nobody wrote are never read.
+__global__ __launch_bounds__(256) void attn_bwd_dq_reduce_varlen_kernel(float* __restrict__ dq,
+                                                                        const float* __restrict__ part, int N, int M,
+                                                                        int64_t slot, int P,
+                                                                        const int* __restrict__ qlen,
+                                                                        const int* __restrict__ klen) {
+  const int b = blockIdx.z, n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const int Ne = qlen ? min(max(qlen[b], 0), N) : N;
+  const int Me = klen ? min(max(klen[b], 0), M) : M;
+  const int Pe = min(P, (Me + kKB - 1) / kKB);
+  const int64_t i = ((int64_t)b * gridDim.y + blockIdx.y) * N + n;
+  float s = 0.f;
+  if (n < Ne && Pe > 0) {
+    s = dq[i];
+    for (int p = 1; p < Pe; ++p) s += part[(int64_t)(p - 1) * slot + i];
+    s *= kScale;
+  }
+  dq[i] = s;
+}
+
 }  // namespace
 
 extern "C" int pk_attention_fwd(const float* q, const float* k, const float* v, int B, int D, int H,
@@ -456,8 +536,21 @@ extern "C" int pk_attention_fwd(const float* q, const float* k, const float* v, 
   if (B == 0 || N == 0) return PK_OK;
   PK_REQUIRE(M > 0 && q && k && v && out && lse);
   const int64_t dense = (int64_t)kD * H * M;
-  hipLaunchKernelGGL(attn_fwd_kernel, dim3((N + kFQ - 1) / kFQ, H, B), dim3(512), 0, pk::as_stream(stream),
-                     q, k, v, H, N, M, sbk ? sbk : dense, sbv ? sbv : dense, out, lse);
+  hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3((N + kFQ - 1) / kFQ, H, B), dim3(512), 0, pk::as_stream(stream),
+                     q, k, v, H, N, M, sbk ? sbk : dense, sbv ? sbv : dense, out, lse, nullptr, nullptr);
+  PK_CHECK_LAUNCH();
+  return PK_OK;
+}
+
+extern "C" int pk_attention_fwd_varlen(const float* q, const float* k, const float* v, int B, int D, int H, int N,
+                                       int M, int64_t sbk, int64_t sbv, const int* qlen, const int* klen, float* out,
+                                       float* lse, void* stream) {
+  PK_REQUIRE(B >= 0 && H > 0 && N >= 0 && M >= 0 && D == kD && sbk >= 0 && sbv >= 0);
+  if (B == 0 || N == 0) return PK_OK;
+  PK_REQUIRE(M > 0 && q && k && v && out && lse);
+  const int64_t dense = (int64_t)kD * H * M;
+  hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3((N + kFQ - 1) / kFQ, H, B), dim3(512), 0, pk::as_stream(stream),
+                     q, k, v, H, N, M, sbk ? sbk : dense, sbv ? sbv : dense, out, lse, qlen, klen);
   PK_CHECK_LAUNCH();
   return PK_OK;
 }
@@ -479,8 +572,9 @@ extern "C" int pk_attention_bwd(const float* q, const float* k, const float* v, 
   PK_REQUIRE((int64_t)P * B * H <= (int64_t)INT32_MAX && (int64_t)H * N <= (int64_t)INT32_MAX);
   hipStream_t s = pk::as_stream(stream);
   const int64_t dense = (int64_t)kD * H * M;
-  hipLaunchKernelGGL(attn_bwd_kernel, dim3(P, H, B), dim3(512), 0, s, q, k, v, out, dout, lse, H, N, M,
-                     sbk ? sbk : dense, sbv ? sbv : dense, sbdk ? sbdk : dense, sbdv ? sbdv : dense, dq, work, dk, dv);
+  hipLaunchKernelGGL(attn_bwd_kernel<false>, dim3(P, H, B), dim3(512), 0, s, q, k, v, out, dout, lse, H, N, M,
+                     sbk ? sbk : dense, sbv ? sbv : dense, sbdk ? sbdk : dense, sbdv ? sbdv : dense, dq, work, dk, dv,
+                     nullptr, nullptr);
   PK_CHECK_LAUNCH();
   if (P > 1) {
     const int64_t n = (int64_t)B * kD * H * N;
@@ -493,5 +587,28 @@ extern "C" int pk_attention_bwd(const float* q, const float* k, const float* v, 
     }
     PK_CHECK_LAUNCH();
   }
+  return PK_OK;
+}
+
+extern "C" int pk_attention_bwd_varlen(const float* q, const float* k, const float* v, const float* out,
+                                       const float* dout, const float* lse, int B, int D, int H, int N, int M,
+                                       int64_t sbk, int64_t sbv, const int* qlen, const int* klen, float* work,
+                                       float* dq, float* dk, float* dv, int64_t sbdk, int64_t sbdv, void* stream) {
+  PK_REQUIRE(B >= 0 && H > 0 && N >= 0 && M >= 0 && D == kD && sbk >= 0 && sbv >= 0 && sbdk >= 0 && sbdv >= 0);
+  if (B == 0 || N == 0 || M == 0) return PK_OK;
+  const int P = (M + kKB - 1) / kKB;
+  PK_REQUIRE(q && k && v && out && dout && lse && dq && dk && dv && (work || P == 1));
+  PK_REQUIRE((int64_t)P * B * H <= (int64_t)INT32_MAX && (int64_t)H * N <= (int64_t)INT32_MAX);
+  PK_REQUIRE(B <= 65535 && kD * H <= 65535);  // the reduce's grid: (query chunks, channels, crops)
+  hipStream_t s = pk::as_stream(stream);
+  const int64_t dense = (int64_t)kD * H * M;
+  hipLaunchKernelGGL(attn_bwd_kernel<true>, dim3(P, H, B), dim3(512), 0, s, q, k, v, out, dout, lse, H, N, M,
+                     sbk ? sbk : dense, sbv ? sbv : dense, sbdk ? sbdk : dense, sbdv ? sbdv : dense, dq, work, dk, dv,
+                     qlen, klen);
+  PK_CHECK_LAUNCH();
+  // always reduced, one key block included: this launch also writes the zeros of rows >= qlen[b]
+  hipLaunchKernelGGL(attn_bwd_dq_reduce_varlen_kernel, dim3((N + 255) / 256, kD * H, B), dim3(256), 0, s, dq, work, N,
+                     M, (int64_t)B * kD * H * N, P, qlen, klen);
+  PK_CHECK_LAUNCH();
   return PK_OK;
 }

@@ -6,44 +6,69 @@
 //   forward   mean = sum x / N, var = sum (x - mean)^2 / N (biased, two passes over the row
 //             held in registers), invstd = 1 / sqrt(var + eps), y = max((x - mean) invstd, 0)
 //   backward  g = dy [xhat > 0], dx = invstd (g - mean(g) - xhat mean(g xhat))
+// Masked mode (VARLEN, pk_instnorm_relu_*_varlen; a build-defined deviation from the reference):
+// row r belongs to crop r / C with n = lens[r / C] real points. Every mean above is over those n
+// points and divided by n, points >= n are not loaded, and y / dx are written as 0 there. n == 0:
+// mean = 0, invstd = 1 / sqrt(eps), all outputs 0. The !VARLEN instantiations have n = N folded.
 #include "common.hpp"
 
 namespace {
 
 constexpr int kMaxPerLane = 32;  // N <= 2048 held in registers (64 lanes x 32)
 
-template <int PER>
+// the row's real length: N, or in masked mode its crop's lens entry clamped to [0, N]
+template <bool VARLEN>
+__device__ __forceinline__ int row_len(int64_t r, int N, int C, const int* __restrict__ lens) {
+  if constexpr (VARLEN) {
+    if (lens) return min(max(lens[r / C], 0), N);
+  }
+  return N;
+}
+
+// sum / n; masked mode defines the mean of an empty row as 0
+template <bool VARLEN>
+__device__ __forceinline__ float mean_of(float sum, int n) {
+  if constexpr (VARLEN) {
+    if (n == 0) return 0.f;
+  }
+  return sum / (float)n;
+}
+
+template <int PER, bool VARLEN>
 __global__ __launch_bounds__(256) void instnorm_relu_fwd_kernel(const float* __restrict__ x, int64_t rows, int N,
                                                                 float eps, float* __restrict__ y,
                                                                 float* __restrict__ mean_out,
-                                                                float* __restrict__ invstd_out) {
+                                                                float* __restrict__ invstd_out, int C,
+                                                                const int* __restrict__ lens) {
   const int64_t r = (int64_t)blockIdx.x * 4 + pk::wave_id();
   if (r >= rows) return;
   const int lane = pk::lane_id();
+  const int Ne = row_len<VARLEN>(r, N, C, lens);
   const float* __restrict__ xr = x + r * N;
   float v[PER];
   float s = 0.f;
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     const int n = lane + 64 * k;
-    v[k] = n < N ? xr[n] : 0.f;
+    v[k] = n < Ne ? xr[n] : 0.f;
     s += v[k];
   }
-  const float mean = pk::wave_sum_f32(s) / (float)N;
+  const float mean = mean_of<VARLEN>(pk::wave_sum_f32(s), Ne);
   float q = 0.f;
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     const int n = lane + 64 * k;
     const float d = v[k] - mean;
-    q += n < N ? d * d : 0.f;
+    q += n < Ne ? d * d : 0.f;
   }
-  const float var = pk::wave_sum_f32(q) / (float)N;
+  const float var = mean_of<VARLEN>(pk::wave_sum_f32(q), Ne);
   const float invstd = 1.f / sqrtf(var + eps);
   float* __restrict__ yr = y + r * N;
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     const int n = lane + 64 * k;
-    if (n < N) yr[n] = fmaxf((v[k] - mean) * invstd, 0.f);
+    if (n < Ne) yr[n] = fmaxf((v[k] - mean) * invstd, 0.f);
+    else if (VARLEN && n < N) yr[n] = 0.f;
   }
   if (lane == 0) {
     mean_out[r] = mean;
@@ -51,15 +76,17 @@ __global__ __launch_bounds__(256) void instnorm_relu_fwd_kernel(const float* __r
   }
 }
 
-template <int PER>
+template <int PER, bool VARLEN>
 __global__ __launch_bounds__(256) void instnorm_relu_bwd_kernel(const float* __restrict__ x,
                                                                 const float* __restrict__ dy,
                                                                 const float* __restrict__ mean_in,
                                                                 const float* __restrict__ invstd_in, int64_t rows,
-                                                                int N, float* __restrict__ dx) {
+                                                                int N, float* __restrict__ dx, int C,
+                                                                const int* __restrict__ lens) {
   const int64_t r = (int64_t)blockIdx.x * 4 + pk::wave_id();
   if (r >= rows) return;
   const int lane = pk::lane_id();
+  const int Ne = row_len<VARLEN>(r, N, C, lens);
   const float mean = mean_in[r], invstd = invstd_in[r];
   const float* __restrict__ xr = x + r * N;
   const float* __restrict__ gr = dy + r * N;
@@ -68,73 +95,124 @@ __global__ __launch_bounds__(256) void instnorm_relu_bwd_kernel(const float* __r
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     const int n = lane + 64 * k;
-    const float xv = n < N ? xr[n] : 0.f;
-    const float gv = n < N ? gr[n] : 0.f;
+    const float xv = n < Ne ? xr[n] : 0.f;
+    const float gv = n < Ne ? gr[n] : 0.f;  // (0 past Ne: g = 0 there whatever xhat's sign)
     xh[k] = (xv - mean) * invstd;
     g[k] = xh[k] > 0.f ? gv : 0.f;  // ReLU backward on the normalized value (= the output)
     sg += g[k];
     sgx += g[k] * xh[k];
   }
-  const float mg = pk::wave_sum_f32(sg) / (float)N;
-  const float mgx = pk::wave_sum_f32(sgx) / (float)N;
+  const float mg = mean_of<VARLEN>(pk::wave_sum_f32(sg), Ne);
+  const float mgx = mean_of<VARLEN>(pk::wave_sum_f32(sgx), Ne);
   float* __restrict__ dr = dx + r * N;
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     const int n = lane + 64 * k;
-    if (n < N) dr[n] = invstd * ((g[k] - mg) - xh[k] * mgx);
+    if (n < Ne) dr[n] = invstd * ((g[k] - mg) - xh[k] * mgx);
+    else if (VARLEN && n < N) dr[n] = 0.f;
   }
 }
 
 // rows longer than the register tile (N > 2048, e.g. 4096-point crops): the same arithmetic
 // re-reading the row from memory (L2-resident) for each pass
+template <bool VARLEN>
 __global__ __launch_bounds__(256) void instnorm_relu_fwd_long_kernel(const float* __restrict__ x, int64_t rows, int N,
                                                                      float eps, float* __restrict__ y,
                                                                      float* __restrict__ mean_out,
-                                                                     float* __restrict__ invstd_out) {
+                                                                     float* __restrict__ invstd_out, int C,
+                                                                     const int* __restrict__ lens) {
   const int64_t r = (int64_t)blockIdx.x * 4 + pk::wave_id();
   if (r >= rows) return;
   const int lane = pk::lane_id();
+  const int Ne = row_len<VARLEN>(r, N, C, lens);
   const float* __restrict__ xr = x + r * N;
   float s = 0.f;
-  for (int n = lane; n < N; n += 64) s += xr[n];
-  const float mean = pk::wave_sum_f32(s) / (float)N;
+  for (int n = lane; n < Ne; n += 64) s += xr[n];
+  const float mean = mean_of<VARLEN>(pk::wave_sum_f32(s), Ne);
   float q = 0.f;
-  for (int n = lane; n < N; n += 64) {
+  for (int n = lane; n < Ne; n += 64) {
     const float d = xr[n] - mean;
     q += d * d;
   }
-  const float invstd = 1.f / sqrtf(pk::wave_sum_f32(q) / (float)N + eps);
-  for (int n = lane; n < N; n += 64) y[r * N + n] = fmaxf((xr[n] - mean) * invstd, 0.f);
+  const float invstd = 1.f / sqrtf(mean_of<VARLEN>(pk::wave_sum_f32(q), Ne) + eps);
+  for (int n = lane; n < Ne; n += 64) y[r * N + n] = fmaxf((xr[n] - mean) * invstd, 0.f);
+  if constexpr (VARLEN) {
+    for (int n = Ne + lane; n < N; n += 64) y[r * N + n] = 0.f;
+  }
   if (lane == 0) {
     mean_out[r] = mean;
     invstd_out[r] = invstd;
   }
 }
 
+template <bool VARLEN>
 __global__ __launch_bounds__(256) void instnorm_relu_bwd_long_kernel(const float* __restrict__ x,
                                                                      const float* __restrict__ dy,
                                                                      const float* __restrict__ mean_in,
                                                                      const float* __restrict__ invstd_in,
-                                                                     int64_t rows, int N, float* __restrict__ dx) {
+                                                                     int64_t rows, int N, float* __restrict__ dx, int C,
+                                                                     const int* __restrict__ lens) {
   const int64_t r = (int64_t)blockIdx.x * 4 + pk::wave_id();
   if (r >= rows) return;
   const int lane = pk::lane_id();
+  const int Ne = row_len<VARLEN>(r, N, C, lens);
   const float mean = mean_in[r], invstd = invstd_in[r];
   const float* __restrict__ xr = x + r * N;
   const float* __restrict__ gr = dy + r * N;
   float sg = 0.f, sgx = 0.f;
-  for (int n = lane; n < N; n += 64) {
+  for (int n = lane; n < Ne; n += 64) {
     const float xh = (xr[n] - mean) * invstd;
     const float g = xh > 0.f ? gr[n] : 0.f;
     sg += g;
     sgx += g * xh;
   }
-  const float mg = pk::wave_sum_f32(sg) / (float)N, mgx = pk::wave_sum_f32(sgx) / (float)N;
-  for (int n = lane; n < N; n += 64) {
+  const float mg = mean_of<VARLEN>(pk::wave_sum_f32(sg), Ne), mgx = mean_of<VARLEN>(pk::wave_sum_f32(sgx), Ne);
+  for (int n = lane; n < Ne; n += 64) {
     const float xh = (xr[n] - mean) * invstd;
     const float g = xh > 0.f ? gr[n] : 0.f;
     dx[r * N + n] = invstd * ((g - mg) - xh * mgx);
   }
+  if constexpr (VARLEN) {
+    for (int n = Ne + lane; n < N; n += 64) dx[r * N + n] = 0.f;
+  }
+}
+
+}  // namespace
+
+namespace {
+
+template <bool VARLEN>
+int instnorm_fwd_launch(const float* x, int64_t rows, int N, float eps, float* y, float* mean, float* invstd, int C,
+                        const int* lens, void* stream) {
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  hipStream_t s = pk::as_stream(stream);
+  if (N <= 512)
+    hipLaunchKernelGGL((instnorm_relu_fwd_kernel<8, VARLEN>), grid, dim3(256), 0, s, x, rows, N, eps, y, mean, invstd, C, lens);
+  else if (N <= 1024)
+    hipLaunchKernelGGL((instnorm_relu_fwd_kernel<16, VARLEN>), grid, dim3(256), 0, s, x, rows, N, eps, y, mean, invstd, C, lens);
+  else if (N <= 2048)
+    hipLaunchKernelGGL((instnorm_relu_fwd_kernel<32, VARLEN>), grid, dim3(256), 0, s, x, rows, N, eps, y, mean, invstd, C, lens);
+  else
+    hipLaunchKernelGGL(instnorm_relu_fwd_long_kernel<VARLEN>, grid, dim3(256), 0, s, x, rows, N, eps, y, mean, invstd, C, lens);
+  PK_CHECK_LAUNCH();
+  return PK_OK;
+}
+
+template <bool VARLEN>
+int instnorm_bwd_launch(const float* x, const float* dy, const float* mean, const float* invstd, int64_t rows, int N,
+                        float* dx, int C, const int* lens, void* stream) {
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  hipStream_t s = pk::as_stream(stream);
+  if (N <= 512)
+    hipLaunchKernelGGL((instnorm_relu_bwd_kernel<8, VARLEN>), grid, dim3(256), 0, s, x, dy, mean, invstd, rows, N, dx, C, lens);
+  else if (N <= 1024)
+    hipLaunchKernelGGL((instnorm_relu_bwd_kernel<16, VARLEN>), grid, dim3(256), 0, s, x, dy, mean, invstd, rows, N, dx, C, lens);
+  else if (N <= 2048)
+    hipLaunchKernelGGL((instnorm_relu_bwd_kernel<32, VARLEN>), grid, dim3(256), 0, s, x, dy, mean, invstd, rows, N, dx, C, lens);
+  else
+    hipLaunchKernelGGL(instnorm_relu_bwd_long_kernel<VARLEN>, grid, dim3(256), 0, s, x, dy, mean, invstd, rows, N, dx, C, lens);
+  PK_CHECK_LAUNCH();
+  return PK_OK;
 }
 
 }  // namespace
@@ -144,14 +222,7 @@ extern "C" int pk_instnorm_relu_fwd(const float* x, int64_t rows, int N, float e
   PK_REQUIRE(rows >= 0 && N > 0);
   if (rows == 0) return PK_OK;
   PK_REQUIRE(x && y && mean && invstd);
-  const dim3 grid((unsigned)((rows + 3) / 4));
-  hipStream_t s = pk::as_stream(stream);
-  if (N <= 512) hipLaunchKernelGGL(instnorm_relu_fwd_kernel<8>, grid, dim3(256), 0, s, x, rows, N, eps, y, mean, invstd);
-  else if (N <= 1024) hipLaunchKernelGGL(instnorm_relu_fwd_kernel<16>, grid, dim3(256), 0, s, x, rows, N, eps, y, mean, invstd);
-  else if (N <= 2048) hipLaunchKernelGGL(instnorm_relu_fwd_kernel<32>, grid, dim3(256), 0, s, x, rows, N, eps, y, mean, invstd);
-  else hipLaunchKernelGGL(instnorm_relu_fwd_long_kernel, grid, dim3(256), 0, s, x, rows, N, eps, y, mean, invstd);
-  PK_CHECK_LAUNCH();
-  return PK_OK;
+  return instnorm_fwd_launch<false>(x, rows, N, eps, y, mean, invstd, 1, nullptr, stream);
 }
 
 extern "C" int pk_instnorm_relu_bwd(const float* x, const float* dy, const float* mean, const float* invstd,
@@ -159,14 +230,23 @@ extern "C" int pk_instnorm_relu_bwd(const float* x, const float* dy, const float
   PK_REQUIRE(rows >= 0 && N > 0);
   if (rows == 0) return PK_OK;
   PK_REQUIRE(x && dy && mean && invstd && dx);
-  const dim3 grid((unsigned)((rows + 3) / 4));
-  hipStream_t s = pk::as_stream(stream);
-  if (N <= 512) hipLaunchKernelGGL(instnorm_relu_bwd_kernel<8>, grid, dim3(256), 0, s, x, dy, mean, invstd, rows, N, dx);
-  else if (N <= 1024) hipLaunchKernelGGL(instnorm_relu_bwd_kernel<16>, grid, dim3(256), 0, s, x, dy, mean, invstd, rows, N, dx);
-  else if (N <= 2048) hipLaunchKernelGGL(instnorm_relu_bwd_kernel<32>, grid, dim3(256), 0, s, x, dy, mean, invstd, rows, N, dx);
-  else hipLaunchKernelGGL(instnorm_relu_bwd_long_kernel, grid, dim3(256), 0, s, x, dy, mean, invstd, rows, N, dx);
-  PK_CHECK_LAUNCH();
-  return PK_OK;
+  return instnorm_bwd_launch<false>(x, dy, mean, invstd, rows, N, dx, 1, nullptr, stream);
+}
+
+extern "C" int pk_instnorm_relu_fwd_varlen(const float* x, int64_t rows, int N, float eps, float* y, float* mean,
+                                           float* invstd, int C, const int* lens, void* stream) {
+  PK_REQUIRE(rows >= 0 && N > 0 && C > 0 && rows % C == 0);
+  if (rows == 0) return PK_OK;
+  PK_REQUIRE(x && y && mean && invstd);
+  return instnorm_fwd_launch<true>(x, rows, N, eps, y, mean, invstd, C, lens, stream);
+}
+
+extern "C" int pk_instnorm_relu_bwd_varlen(const float* x, const float* dy, const float* mean, const float* invstd,
+                                           int64_t rows, int N, float* dx, int C, const int* lens, void* stream) {
+  PK_REQUIRE(rows >= 0 && N > 0 && C > 0 && rows % C == 0);
+  if (rows == 0) return PK_OK;
+  PK_REQUIRE(x && dy && mean && invstd && dx);
+  return instnorm_bwd_launch<true>(x, dy, mean, invstd, rows, N, dx, C, lens, stream);
 }
 
 // ---------------------------------------------------------------------------------
@@ -177,6 +257,8 @@ extern "C" int pk_instnorm_relu_bwd(const float* x, const float* dy, const float
 //   bce_n = (t_n - 1) max(log1p(-p_n), -100) - t_n max(log p_n, -100)   (ATen's formula)
 //   loss = sum_n w_n bce_n / N;  dloss/dp_n = w_n (p_n - t_n) / max(p_n (1 - p_n), 1e-12) / N
 // Sums in a fixed order (deterministic).
+// Masked mode (VARLEN, pk_wbce_varlen): wn, the mean and the gradient's 1 / N use the crop's true
+// count n1[b] / n2[b] (N stays the row stride); gradients past it are 0; an empty crop's loss is 0.
 namespace {
 
 constexpr int kBceThreads = 256;
@@ -192,23 +274,36 @@ __device__ __forceinline__ float block_sum_f32(float v, float* red) {
   return s;
 }
 
+template <bool VARLEN>
 __global__ __launch_bounds__(kBceThreads) void wbce_kernel(const float* __restrict__ p0, const int8_t* __restrict__ t0,
                                                            int N0, const float* __restrict__ p1,
                                                            const int8_t* __restrict__ t1, int N1, int B,
                                                            float* __restrict__ loss, float* __restrict__ g0,
-                                                           float* __restrict__ g1) {
+                                                           float* __restrict__ g1, const int* __restrict__ len0,
+                                                           const int* __restrict__ len1) {
   __shared__ float red[kBceThreads / 64];
   const int b = blockIdx.x % B, which = blockIdx.x / B;
   const int N = which ? N1 : N0;
+  int Ne = N;
+  if constexpr (VARLEN) {
+    const int* __restrict__ len = which ? len1 : len0;
+    if (len) Ne = min(max(len[b], 0), N);
+  }
   const float* __restrict__ p = (which ? p1 : p0) + (int64_t)b * N;
   const int8_t* __restrict__ t = (which ? t1 : t0) + (int64_t)b * N;
   float* __restrict__ g = g0 ? (which ? g1 : g0) + (int64_t)b * N : nullptr;
   float st = 0.f;
-  for (int n = threadIdx.x; n < N; n += kBceThreads) st += (float)t[n];
-  const float wn = block_sum_f32(st, red) / (float)N;
+  for (int n = threadIdx.x; n < Ne; n += kBceThreads) st += (float)t[n];
+  const bool empty = VARLEN && Ne == 0;
+  const float ssum = block_sum_f32(st, red);
+  const float wn = empty ? 0.f : ssum / (float)Ne;
   float sl = 0.f;
-  const float invN = 1.f / (float)N;
-  for (int n = threadIdx.x; n < N; n += kBceThreads) {
+  const float invN = empty ? 0.f : 1.f / (float)Ne;
+  if constexpr (VARLEN) {
+    if (g)
+      for (int n = Ne + threadIdx.x; n < N; n += kBceThreads) g[n] = 0.f;
+  }
+  for (int n = threadIdx.x; n < Ne; n += kBceThreads) {
     const float pv = p[n], tv = (float)t[n];
     const float w = tv >= 0.5f ? 1.f - wn : wn;
     const float l = (tv - 1.f) * fmaxf(log1pf(-pv), -100.f) - tv * fmaxf(logf(pv), -100.f);
@@ -226,8 +321,20 @@ extern "C" int pk_wbce(const float* p12, const int8_t* t12, int N1, const float*
   PK_REQUIRE(B >= 0 && N1 > 0 && N2 > 0 && (g12 == nullptr) == (g21 == nullptr));
   if (B == 0) return PK_OK;
   PK_REQUIRE(p12 && t12 && p21 && t21 && loss);
-  hipLaunchKernelGGL(wbce_kernel, dim3(2 * B), dim3(kBceThreads), 0, pk::as_stream(stream), p12, t12, N1, p21, t21,
-                     N2, B, loss, g12, g21);
+  hipLaunchKernelGGL(wbce_kernel<false>, dim3(2 * B), dim3(kBceThreads), 0, pk::as_stream(stream), p12, t12, N1, p21,
+                     t21, N2, B, loss, g12, g21, nullptr, nullptr);
+  PK_CHECK_LAUNCH();
+  return PK_OK;
+}
+
+extern "C" int pk_wbce_varlen(const float* p12, const int8_t* t12, int N1, const float* p21, const int8_t* t21,
+                              int N2, int B, const int* n1, const int* n2, float* loss, float* g12, float* g21,
+                              void* stream) {
+  PK_REQUIRE(B >= 0 && N1 > 0 && N2 > 0 && (g12 == nullptr) == (g21 == nullptr));
+  if (B == 0) return PK_OK;
+  PK_REQUIRE(p12 && t12 && p21 && t21 && loss);
+  hipLaunchKernelGGL(wbce_kernel<true>, dim3(2 * B), dim3(kBceThreads), 0, pk::as_stream(stream), p12, t12, N1, p21,
+                     t21, N2, B, loss, g12, g21, n1, n2);
   PK_CHECK_LAUNCH();
   return PK_OK;
 }

@@ -70,6 +70,9 @@ SIGNATURES = {
     "pk_fmap_solve_backward": [_P, _P, _P, _F, _I, _I, _P, _P, _P, _P],
     "pk_attention_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I64, _I64, _P, _P, _P],
     "pk_attention_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _P],
+    "pk_attention_fwd_varlen": [_P, _P, _P, _I, _I, _I, _I, _I, _I64, _I64, _P, _P, _P, _P, _P],
+    "pk_attention_bwd_varlen": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64,
+                                _I64, _P],
     "pk_linear_wgrad": [_P, _P, _I, _I64, _I, _I, _I, _P, _P, _P, _I, _P],
     "pk_linear_wgrad_grouped_work": [_P, _I],
     "pk_linear_wgrad_grouped": [_P, _I, _P, _I64, _P],
@@ -80,7 +83,10 @@ SIGNATURES = {
     "pk_clip_rmsprop": [_P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _P, _P, _P],
     "pk_instnorm_relu_fwd": [_P, _I64, _I, _F, _P, _P, _P, _P],
     "pk_instnorm_relu_bwd": [_P, _P, _P, _P, _I64, _I, _P, _P],
+    "pk_instnorm_relu_fwd_varlen": [_P, _I64, _I, _F, _P, _P, _P, _I, _P, _P],
+    "pk_instnorm_relu_bwd_varlen": [_P, _P, _P, _P, _I64, _I, _P, _I, _P, _P],
     "pk_wbce": [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P],
+    "pk_wbce_varlen": [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
     "pk_l2_normalize_fwd": [_P, _P, _I, _I, _I, _P, _P, _P, _P],
     "pk_l2_normalize_bwd": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
     "pk_overlap_head_fwd": [_P, _P],

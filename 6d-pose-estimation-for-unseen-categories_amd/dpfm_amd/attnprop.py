@@ -33,8 +33,12 @@ def _wgrad(x, dy, weight, bias):
     return dw.view(weight.shape), db
 
 
-def _prop_fwd(x, src, P, heads, eps):
-    """desc' = x + layer(x, src) in the launches above; returns (desc', saved tensors)."""
+def _prop_fwd(x, src, P, heads, eps, nx=None, nsrc=None):
+    """desc' = x + layer(x, src) in the launches above; returns (desc', saved tensors).
+    nx / nsrc (masked mode; int32 [B] on the device or None): the real points of x (the queries,
+    and the rows the norm's statistics run over) and of src (the keys) — the attention and the norm
+    then go to their varlen entry points; every other launch is per point. The `work=` figures
+    keep the padded shapes in masked mode (an upper bound: the lengths live on the device)."""
     wq, bq, wk, bk, wv, bv, wm, bm, w0, b0, w3, b3 = P
     B, C, N = x.shape
     M = src.shape[2]
@@ -50,8 +54,13 @@ def _prop_fwd(x, src, P, heads, eps):
     lse = torch.empty((B, heads, N, 2), dtype=torch.float32, device=dev)
     import ctypes
     vptr = ctypes.c_void_p(kv.data_ptr() + 4 * C * M)
-    call("pk_attention_fwd", ptr(q), ptr(kv), vptr, B, D, heads, N, M, 2 * C * M, 2 * C * M, ptr(a), ptr(lse),
-         _lib.stream(dev), work=("mfma", 2 * 2 * N * M * D * B * heads))
+    masked = nx is not None or nsrc is not None
+    if masked:
+        call("pk_attention_fwd_varlen", ptr(q), ptr(kv), vptr, B, D, heads, N, M, 2 * C * M, 2 * C * M, ptr(nx),
+             ptr(nsrc), ptr(a), ptr(lse), _lib.stream(dev), work=("mfma", 2 * 2 * N * M * D * B * heads))
+    else:
+        call("pk_attention_fwd", ptr(q), ptr(kv), vptr, B, D, heads, N, M, 2 * C * M, 2 * C * M, ptr(a), ptr(lse),
+             _lib.stream(dev), work=("mfma", 2 * 2 * N * M * D * B * heads))
     hc = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)  # cat(desc, message)
     call("pk_copy_rows", ptr(hc), 2 * C * N, ptr(x), C * N, B, C * N, _lib.stream(dev),
          work=("hbm", 8 * B * C * N))
@@ -61,14 +70,18 @@ def _prop_fwd(x, src, P, heads, eps):
     h1n = torch.empty_like(h1)
     mean = torch.empty((B * 2 * C,), dtype=torch.float32, device=dev)
     invstd = torch.empty_like(mean)
-    call("pk_instnorm_relu_fwd", ptr(h1), B * 2 * C, N, float(eps), ptr(h1n), ptr(mean), ptr(invstd),
-         _lib.stream(dev), work=("hbm", 8 * B * 2 * C * N))
+    if masked:
+        call("pk_instnorm_relu_fwd_varlen", ptr(h1), B * 2 * C, N, float(eps), ptr(h1n), ptr(mean), ptr(invstd),
+             2 * C, ptr(nx), _lib.stream(dev), work=("hbm", 8 * B * 2 * C * N))
+    else:
+        call("pk_instnorm_relu_fwd", ptr(h1), B * 2 * C, N, float(eps), ptr(h1n), ptr(mean), ptr(invstd),
+             _lib.stream(dev), work=("hbm", 8 * B * 2 * C * N))
     out = torch.empty((B, C, N), dtype=torch.float32, device=dev)
     ops.linear_ex(h1n, f(w3), b3, 1, B * N, N, 2 * C, C, y=out, add=x, add_cols=C)
     return out, (x, src, q, kv, a, lse, hc, h1, h1n, mean, invstd)
 
 
-def _prop_bwd(saved, P, heads, dout, dsrc_add=None):
+def _prop_bwd(saved, P, heads, dout, dsrc_add=None, nx=None, nsrc=None):
     """Gradients of one call: (d x, d src (+ dsrc_add, added in the launch's epilogue), the 12
     parameter gradients — None where the active GroupedWgrad takes them)."""
     x, src, q, kv, a, lse, hc, h1, h1n, mean, invstd = saved
@@ -84,8 +97,13 @@ def _prop_bwd(saved, P, heads, dout, dsrc_add=None):
     ops.linear_ex(dout, f(w3), None, 1, B * N, N, C, 2 * C, y=dh1n, transw=True)
     g_w3, g_b3 = _wgrad(h1n, dout, w3, b3)
     dh1 = torch.empty_like(dh1n)
-    call("pk_instnorm_relu_bwd", ptr(h1), ptr(dh1n), ptr(mean), ptr(invstd), B * 2 * C, N, ptr(dh1),
-         _lib.stream(dev), work=("hbm", 12 * B * 2 * C * N))
+    masked = nx is not None or nsrc is not None  # (work= figures: padded shapes, as in _prop_fwd)
+    if masked:
+        call("pk_instnorm_relu_bwd_varlen", ptr(h1), ptr(dh1n), ptr(mean), ptr(invstd), B * 2 * C, N, ptr(dh1),
+             2 * C, ptr(nx), _lib.stream(dev), work=("hbm", 12 * B * 2 * C * N))
+    else:
+        call("pk_instnorm_relu_bwd", ptr(h1), ptr(dh1n), ptr(mean), ptr(invstd), B * 2 * C, N, ptr(dh1),
+             _lib.stream(dev), work=("hbm", 12 * B * 2 * C * N))
     dhc = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
     ops.linear_ex(dh1, f(w0), None, 1, B * N, N, 2 * C, 2 * C, y=dhc, transw=True)
     g_w0, g_b0 = _wgrad(hc, dh1, w0, b0)
@@ -99,10 +117,16 @@ def _prop_bwd(saved, P, heads, dout, dsrc_add=None):
     work = ops.attention_bwd_work(B, D, heads, N, M, dev)
     import ctypes
     off = 4 * C * M
-    call("pk_attention_bwd", ptr(q), ptr(kv), ctypes.c_void_p(kv.data_ptr() + off), ptr(a), ptr(da), ptr(lse),
-         B, D, heads, N, M, 2 * C * M, 2 * C * M, ptr(work), ptr(dq), ptr(dkv),
-         ctypes.c_void_p(dkv.data_ptr() + off), 2 * C * M, 2 * C * M, _lib.stream(dev),
-         work=("mfma", 5 * 2 * N * M * D * B * heads))  # S, dP, dV, dK, dQ: each contraction once
+    if masked:
+        call("pk_attention_bwd_varlen", ptr(q), ptr(kv), ctypes.c_void_p(kv.data_ptr() + off), ptr(a), ptr(da),
+             ptr(lse), B, D, heads, N, M, 2 * C * M, 2 * C * M, ptr(nx), ptr(nsrc), ptr(work), ptr(dq), ptr(dkv),
+             ctypes.c_void_p(dkv.data_ptr() + off), 2 * C * M, 2 * C * M, _lib.stream(dev),
+             work=("mfma", 5 * 2 * N * M * D * B * heads))
+    else:
+        call("pk_attention_bwd", ptr(q), ptr(kv), ctypes.c_void_p(kv.data_ptr() + off), ptr(a), ptr(da), ptr(lse),
+             B, D, heads, N, M, 2 * C * M, 2 * C * M, ptr(work), ptr(dq), ptr(dkv),
+             ctypes.c_void_p(dkv.data_ptr() + off), 2 * C * M, 2 * C * M, _lib.stream(dev),
+             work=("mfma", 5 * 2 * N * M * D * B * heads))  # S, dP, dV, dK, dQ: each contraction once
     # d desc = Pq^T dq + dout (residual) + dhc[:, :C] (concatenation) and d src = Pk^T dk + Pv^T dv
     # (+ the source's other gradient; the stacked weight's transpose, 64 -> 32): independent, one
     # launch (pk_linear_ex2)
@@ -122,18 +146,19 @@ def _prop_bwd(saved, P, heads, dout, dsrc_add=None):
 
 class _AttnPropFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, src, wq, bq, wk, bk, wv, bv, wm, bm, w0, b0, w3, b3, heads, eps):
+    def forward(ctx, x, src, wq, bq, wk, bk, wv, bv, wm, bm, w0, b0, w3, b3, heads, eps, nx=None, nsrc=None):
         P = (wq, bq, wk, bk, wv, bv, wm, bm, w0, b0, w3, b3)
-        out, saved = _prop_fwd(x, src, P, heads, eps)
+        out, saved = _prop_fwd(x, src, P, heads, eps, nx, nsrc)
         ctx.heads = heads
         ctx.params = P
+        ctx.lens = (nx, nsrc)  # (not differentiable, never outputs: plain attributes)
         ctx.save_for_backward(*saved)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        dx, dsrc, g = _prop_bwd(ctx.saved_tensors, ctx.params, ctx.heads, dout)
-        return (dx, dsrc, *g, None, None)
+        dx, dsrc, g = _prop_bwd(ctx.saved_tensors, ctx.params, ctx.heads, dout, None, *ctx.lens)
+        return (dx, dsrc, *g, None, None, None, None)
 
 
 class _AttnPropPairFn(torch.autograd.Function):
@@ -145,12 +170,15 @@ class _AttnPropPairFn(torch.autograd.Function):
     call's, then the first's, autograd's order for a layer applied twice."""
 
     @staticmethod
-    def forward(ctx, x0, x1, wq, bq, wk, bk, wv, bv, wm, bm, w0, b0, w3, b3, heads, eps):
+    def forward(ctx, x0, x1, wq, bq, wk, bk, wv, bv, wm, bm, w0, b0, w3, b3, heads, eps, n0=None, n1=None):
         P = (wq, bq, wk, bk, wv, bv, wm, bm, w0, b0, w3, b3)
-        out0, s0 = _prop_fwd(x0, x1, P, heads, eps)
-        out1, s1 = _prop_fwd(x1, out0, P, heads, eps)
+        # masked mode: the first call's queries are x0 (n0 real points) and its keys x1 (n1); the
+        # second call's are reversed
+        out0, s0 = _prop_fwd(x0, x1, P, heads, eps, n0, n1)
+        out1, s1 = _prop_fwd(x1, out0, P, heads, eps, n1, n0)
         ctx.heads = heads
         ctx.params = P
+        ctx.lens = (n0, n1)
         ctx.save_for_backward(*s0, *s1)
         return out0, out1
 
@@ -158,10 +186,11 @@ class _AttnPropPairFn(torch.autograd.Function):
     def backward(ctx, g0, g1):
         sv = ctx.saved_tensors
         s0, s1 = sv[:11], sv[11:]
-        dx1_b, dout0, gb = _prop_bwd(s1, ctx.params, ctx.heads, g1, dsrc_add=g0)
-        dx0, dx1, ga = _prop_bwd(s0, ctx.params, ctx.heads, dout0, dsrc_add=dx1_b)
+        n0, n1 = ctx.lens
+        dx1_b, dout0, gb = _prop_bwd(s1, ctx.params, ctx.heads, g1, dsrc_add=g0, nx=n1, nsrc=n0)
+        dx0, dx1, ga = _prop_bwd(s0, ctx.params, ctx.heads, dout0, dsrc_add=dx1_b, nx=n0, nsrc=n1)
         g = [b if a is None else (a if b is None else b + a) for a, b in zip(ga, gb)]
-        return (dx0, dx1, *g, None, None)
+        return (dx0, dx1, *g, None, None, None, None)
 
 
 def _fusable(layer, x, src) -> bool:
@@ -181,17 +210,27 @@ def _params(layer):
             mlp[0].weight, mlp[0].bias, mlp[3].weight, mlp[3].bias)
 
 
-def attn_prop_pair(layer, x0: torch.Tensor, x1: torch.Tensor):
+def attn_prop_pair(layer, x0: torch.Tensor, x1: torch.Tensor, nx=None, nsrc=None):
     """(x0', x1') = (x0 + layer(x0, x1), x1 + layer(x1, x0')) — both calls of one refinement layer
-    (modeling/dpfm.py:101-103) as one fused node — or None outside the fused shapes."""
+    (modeling/dpfm.py:101-103) as one fused node — or None outside the fused shapes.
+    nx / nsrc (masked mode): the real points of x0 / x1, int32 [B] on the device."""
     if not (_fusable(layer, x0, x1) and _fusable(layer, x1, x0)):
         return None
-    return _AttnPropPairFn.apply(x0, x1, *_params(layer), layer.attn.num_heads, float(layer.mlp[1].eps))
+    if nx is None and nsrc is None:
+        return _AttnPropPairFn.apply(x0, x1, *_params(layer), layer.attn.num_heads, float(layer.mlp[1].eps))
+    B, dev = x0.shape[0], x0.device
+    return _AttnPropPairFn.apply(x0, x1, *_params(layer), layer.attn.num_heads, float(layer.mlp[1].eps),
+                                 ops._lens(nx, B, dev), ops._lens(nsrc, B, dev))
 
 
-def attn_prop_residual(layer, x: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
+def attn_prop_residual(layer, x: torch.Tensor, src: torch.Tensor, nx=None, nsrc=None) -> torch.Tensor:
     """x + layer(x, src) for a modeling.dpfm.AttentionalPropagation `layer` as one fused node, or
-    None when the shapes / storage fall outside it (the caller then takes the module path)."""
+    None when the shapes / storage fall outside it (the caller then takes the module path).
+    nx / nsrc (masked mode): the real points of x / src, int32 [B] on the device."""
     if not _fusable(layer, x, src):
         return None
-    return _AttnPropFn.apply(x, src, *_params(layer), layer.attn.num_heads, float(layer.mlp[1].eps))
+    if nx is None and nsrc is None:
+        return _AttnPropFn.apply(x, src, *_params(layer), layer.attn.num_heads, float(layer.mlp[1].eps))
+    B, dev = x.shape[0], x.device
+    return _AttnPropFn.apply(x, src, *_params(layer), layer.attn.num_heads, float(layer.mlp[1].eps),
+                             ops._lens(nx, B, dev), ops._lens(nsrc, B, dev))

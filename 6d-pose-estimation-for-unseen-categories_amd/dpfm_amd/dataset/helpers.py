@@ -21,6 +21,7 @@ import torch
 
 # the operator fields the training / eval scripts move to the device (helpers.py:6)
 DEVICE_FIELDS = ("xyz", "faces", "mass", "evals", "evecs", "gradX", "gradY")
+MASKED_FIELDS = ("n",)  # collate(counts=True)'s true lengths: moved with the operator fields
 SPARSE_FIELDS = ("L", "gradX", "gradY")
 
 
@@ -34,10 +35,13 @@ def pad_batch(arrays: Sequence[np.ndarray]) -> torch.Tensor:
     return batch
 
 
-def _shape_part(crops: Sequence[dict]) -> dict:
+def _shape_part(crops: Sequence[dict], counts: bool = False) -> dict:
     first = crops[0]
-    return {key: (pad_batch([c[key] for c in crops]) if isinstance(first[key], np.ndarray) else None)
+    part = {key: (pad_batch([c[key] for c in crops]) if isinstance(first[key], np.ndarray) else None)
             for key in first}
+    if counts:  # the unpadded lengths, for the masked mode (DPFMNet(masked=True))
+        part["n"] = torch.tensor([int(np.asarray(c["xyz"]).shape[0]) for c in crops], dtype=torch.int32)
+    return part
 
 
 def _obj_part(crops: Sequence[dict]) -> dict:
@@ -53,10 +57,12 @@ def _obj_part(crops: Sequence[dict]) -> dict:
     return out
 
 
-def collate(data):
-    """(CAD, PC, Obj) batch of a list of `base_object_dataset` items (helpers.py:22-50)."""
+def collate(data, counts: bool = False):
+    """(CAD, PC, Obj) batch of a list of `base_object_dataset` items (helpers.py:22-50).
+    counts=True: each shape dict gains "n", the int32 [B] unpadded point counts the masked mode
+    reads (the reference keeps no such record: it does not mask its padding)."""
     cads, pcs, objs = zip(*[(item[0], item[1], item[2]) for item in data])
-    return _shape_part(cads), _shape_part(pcs), _obj_part(objs)
+    return _shape_part(cads, counts), _shape_part(pcs, counts), _obj_part(objs)
 
 
 def collate_noprocess(data):
@@ -74,7 +80,7 @@ def shape_to_device(batch: dict, device) -> dict:
     for key in list(batch):
         entry = batch[key]
         if "shape" in key:
-            for field in DEVICE_FIELDS:
+            for field in DEVICE_FIELDS + MASKED_FIELDS:
                 if entry.get(field) is not None:
                     entry[field] = entry[field].to(device)
         elif isinstance(entry, list):

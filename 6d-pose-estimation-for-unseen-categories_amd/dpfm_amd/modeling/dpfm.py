@@ -25,12 +25,13 @@ class InstanceNormReLU(nn.InstanceNorm1d):
     """nn.InstanceNorm1d(C) (affine=False, no running stats: no parameters or buffers, so
     state_dict keys are unchanged) followed by the ReLU of the next Sequential slot, fused in
     one HIP kernel per direction (ops.instnorm_relu); the slot after it holds an Identity so
-    the Sequential's indices (mlp.0 / mlp.3) match the reference's."""
+    the Sequential's indices (mlp.0 / mlp.3) match the reference's.
+    lens (masked mode; int32 [B] on the device): statistics over each crop's real points only."""
 
-    def forward(self, x):
+    def forward(self, x, lens=None):
         if self.affine or self.track_running_stats:
             raise ValueError("the reference's InstanceNorm1d is affine=False, track_running_stats=False")
-        return ops.instnorm_relu(x, self.eps)
+        return ops.instnorm_relu(x, self.eps, lens)
 
 
 FUSED_ATTN_PROP = True  # AttentionalPropagation + residual as one fused node (attnprop.py)
@@ -52,10 +53,11 @@ def MLP(channels: list, do_bn=True):
     return nn.Sequential(*layers)
 
 
-def attention(query, key, value):
+def attention(query, key, value, qlen=None, klen=None):
     """modeling/dpfm.py:29-37. Tensors are [B, d, heads, N]; returns (result, None): the
-    probability matrix is never materialised (the reference's caller discards it)."""
-    return ops.attention(query, key, value), None
+    probability matrix is never materialised (the reference's caller discards it).
+    qlen / klen: masked mode's per-crop real queries / keys (ops.attention)."""
+    return ops.attention(query, key, value, qlen, klen), None
 
 
 class MultiHeadedAttention(nn.Module):
@@ -67,10 +69,10 @@ class MultiHeadedAttention(nn.Module):
         self.merge = Conv1d(d_model, d_model, kernel_size=1)
         self.proj = nn.ModuleList([deepcopy(self.merge) for _ in range(3)])
 
-    def forward(self, query, key, value):
+    def forward(self, query, key, value, qlen=None, klen=None):
         B = query.size(0)
         q, k, v = [ll(x).view(B, self.dim, self.num_heads, -1) for ll, x in zip(self.proj, (query, key, value))]
-        x, _ = attention(q, k, v)
+        x, _ = attention(q, k, v, qlen, klen)
         return self.merge(x.contiguous().view(B, self.dim * self.num_heads, -1))
 
 
@@ -81,21 +83,37 @@ class AttentionalPropagation(nn.Module):
         self.mlp = MLP([feature_dim * 2, feature_dim * 2, feature_dim])
         nn.init.constant_(self.mlp[-1].bias, 0.0)
 
-    def forward(self, x, source):
-        message = self.attn(x, source, source)
-        return self.mlp(torch.cat([x, message], dim=1))
+    def _mlp(self, h, lens, last: bool):
+        """self.mlp (without its last layer unless `last`); masked mode hands the norm its lengths."""
+        mods = list(self.mlp) if last else list(self.mlp)[:-1]
+        for m in mods:
+            h = m(h, lens) if isinstance(m, InstanceNormReLU) else m(h)
+        return h
 
-    def forward_residual(self, x, source):
+    def forward(self, x, source, lengths=None):
+        """lengths = (nx, nsrc) (masked mode): the real points of x / source per crop."""
+        if lengths is None:
+            message = self.attn(x, source, source)
+            return self.mlp(torch.cat([x, message], dim=1))
+        message = self.attn(x, source, source, lengths[0], lengths[1])
+        return self._mlp(torch.cat([x, message], dim=1), lengths[0], last=True)
+
+    def forward_residual(self, x, source, lengths=None):
         """x + forward(x, source) (modeling/dpfm.py:101-103's residual update): one fused autograd
         node (attnprop.attn_prop_residual) where the shapes allow, else the module path with the
-        add folded into the MLP's last layer (layers.pointwise_residual)."""
+        add folded into the MLP's last layer (layers.pointwise_residual). lengths as in forward."""
+        nx, nsrc = lengths if lengths is not None else (None, None)
         if FUSED_ATTN_PROP:
             from ..attnprop import attn_prop_residual
-            y = attn_prop_residual(self, x, source)
+            y = attn_prop_residual(self, x, source, nx, nsrc)
             if y is not None:
                 return y
-        message = self.attn(x, source, source)
-        h = self.mlp[:-1](torch.cat([x, message], dim=1))
+        if lengths is None:
+            message = self.attn(x, source, source)
+            h = self.mlp[:-1](torch.cat([x, message], dim=1))
+        else:
+            message = self.attn(x, source, source, nx, nsrc)
+            h = self._mlp(torch.cat([x, message], dim=1), nx, last=False)
         return pointwise_residual(self.mlp[-1], h, x)
 
 
@@ -123,9 +141,13 @@ class CrossAttentionRefinementNet(nn.Module):
         self.last_lin = Linear(gnn_dim + additional_dim, n_in + additional_dim)
         self.overlap_predictor = OverlapPredictorNet(overlap_feat_dim=overlap_feat_dim)
 
-    def forward(self, coords0, coords1, features_x, features_y, batch=None, features_xy=None):
+    def forward(self, coords0, coords1, features_x, features_y, batch=None, features_xy=None, lengths=None):
         """features_xy (optional): the encoder's [2B, N, C] output of which features_x / features_y
-        are the two halves; first_lin then runs once on it (layers.linear_pair_cf)."""
+        are the two halves; first_lin then runs once on it (layers.linear_pair_cf).
+        lengths = (n1, n2) (masked mode; int32 [B] on the device): the real points of shape 1 / 2.
+        Attention then sees only real keys and the InstanceNorm statistics only real points; the
+        other layers are per point (padded rows carry values nobody reads)."""
+        n1, n2 = lengths if lengths is not None else (None, None)
         pair = None
         if features_xy is not None and FUSED_ATTN_PROP:
             from ..layers import linear_pair_cf
@@ -138,12 +160,15 @@ class CrossAttentionRefinementNet(nn.Module):
             pair = None
             if FUSED_ATTN_PROP:  # both calls of the layer as one node (attnprop.attn_prop_pair)
                 from ..attnprop import attn_prop_pair
-                pair = attn_prop_pair(layer, desc0, desc1)
+                pair = attn_prop_pair(layer, desc0, desc1, n1, n2)
             if pair is not None:
                 desc0, desc1 = pair
-            else:
+            elif lengths is None:
                 desc0 = layer.forward_residual(desc0, desc1)
                 desc1 = layer.forward_residual(desc1, desc0)  # with the updated desc0 (:101-103)
+            else:  # queries shape 1 / keys shape 2, then reversed
+                desc0 = layer.forward_residual(desc0, desc1, (n1, n2))
+                desc1 = layer.forward_residual(desc1, desc0, (n2, n1))
         op = self.overlap_predictor
         ll = self.last_lin
         if (FUSED_ATTN_PROP and self.attention_type == "normal" and ll.out_features == self.n_in

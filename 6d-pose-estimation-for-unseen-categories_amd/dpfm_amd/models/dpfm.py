@@ -5,6 +5,11 @@ config/dpfm_orig.yaml dict, batch = {"shape1": CAD, "shape2": PC} with xyz / mas
 evals / evecs (L, gradX, gradY, faces accepted and unused, as in the reference's
 spectral configuration); returns (C_pred, overlap12, overlap21, use_feat1, use_feat2,
 ref_feat1, ref_feat2). state_dict keys equal weights/weights.pt.
+
+`DPFMNet(cfg, masked=True)` is the masked mode (a build-defined deviation
+from the reference, which lets collate's zero padding into the attention's softmax and the
+InstanceNorm statistics): each shape dict also carries "n", the crops' true point counts, and the
+refiner sees only real points, so a crop's result does not depend on its batch's padding.
 """
 from __future__ import annotations
 
@@ -42,9 +47,10 @@ def _cat0(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 class DPFMNet(nn.Module):
     """Compute the functional map matrix representation."""
 
-    def __init__(self, cfg=None):
+    def __init__(self, cfg=None, masked: bool = False):
         super().__init__()
         cfg = cfg or DEFAULT_CFG
+        self.masked = bool(masked)  # (no parameter or buffer: state_dict keys are unchanged)
         self.feature_extractor = DiffusionNet(C_in=cfg["fmap"]["C_in"], C_out=cfg["fmap"]["n_feat"], C_width=64,
                                               N_block=2, dropout=False, with_gradient_features=False,
                                               with_gradient_rotations=True)
@@ -61,6 +67,14 @@ class DPFMNet(nn.Module):
         s1, s2 = batch["shape1"], batch["shape2"]
         verts1, mass1, evals1, evecs1 = s1["xyz"], s1["mass"], s1["evals"], s1["evecs"]
         verts2, mass2, evals2, evecs2 = s2["xyz"], s2["mass"], s2["evals"], s2["evecs"]
+        lengths = None
+        if self.masked:
+            if s1.get("n") is None or s2.get("n") is None:
+                raise ValueError('masked DPFMNet needs the true point counts batch["shape1"]["n"] and '
+                                 'batch["shape2"]["n"] (int32 [B]; collate(counts=True) / model_batch(masked=True))')
+            if verts1.dim() != 3:
+                raise ValueError("masked DPFMNet takes batched [B, N, 3] shapes")
+            lengths = (s1["n"], s2["n"])
         if verts1.dim() == 3 and verts1.shape == verts2.shape and evecs1.shape == evecs2.shape:
             # same weights, per-crop operations: one pass over both shapes (2B crops); the
             # input features (v - 110) / 50 of both shapes (models/dpfm.py:53) in one launch
@@ -80,7 +94,7 @@ class DPFMNet(nn.Module):
             feat2 = self.feature_extractor(features2, mass2, evals=evals2, evecs=evecs2)
 
         ref_feat1, ref_feat2, overlap_score12, overlap_score21 = self.feat_refiner(
-            verts1, verts2, feat1, feat2, batch, features_xy=feat if fused_cat else None)
+            verts1, verts2, feat1, feat2, batch, features_xy=feat if fused_cat else None, lengths=lengths)
         use_feat1, use_feat2 = (ref_feat1, ref_feat2) if self.robust else (feat1, feat2)
 
         k = self.n_fmap

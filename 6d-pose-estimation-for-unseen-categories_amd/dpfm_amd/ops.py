@@ -455,20 +455,70 @@ class _Attention(torch.autograd.Function):
         return dq, dk, dv
 
 
+def _lens(t, B: int, device) -> Optional[torch.Tensor]:
+    """A per-crop length vector of masked mode as the kernels read it: int32 [B] on `device`,
+    contiguous (None stays None: full length). A device tensor is never synced to the host."""
+    if t is None:
+        return None
+    t = torch.as_tensor(t, device=device)
+    if t.dtype != torch.int32:
+        t = t.to(torch.int32)
+    if t.shape != (B,):
+        raise _lib.PoseKernError(f"per-crop lengths must be [B] = [{B}], got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+class _AttentionVarlen(torch.autograd.Function):
+    """_Attention over each crop's first qlen[b] queries and klen[b] keys (masked mode:
+    pk_attention_fwd_varlen / _bwd_varlen). Padded rows of out / dq / dk / dv are written as 0."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, qlen, klen):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        B, D, H, N = q.shape
+        M = k.shape[3]
+        out = torch.empty_like(q)
+        lse = torch.empty((B, H, N, 2), dtype=torch.float32, device=q.device)
+        # work: the padded shapes (an upper bound of what the lengths leave; they live on the device)
+        call("pk_attention_fwd_varlen", ptr(q), ptr(k), ptr(v), B, D, H, N, M, 0, 0, ptr(qlen), ptr(klen), ptr(out),
+             ptr(lse), _lib.stream(q.device), work=("mfma", 2 * 2 * N * M * D * B * H))
+        ctx.save_for_backward(q, k, v, out, lse, qlen, klen)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, qlen, klen = ctx.saved_tensors
+        dout = dout.contiguous()
+        B, D, H, N = q.shape
+        M = k.shape[3]
+        work = attention_bwd_work(B, D, H, N, M, q.device)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        call("pk_attention_bwd_varlen", ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), B, D, H, N, M, 0, 0,
+             ptr(qlen), ptr(klen), ptr(work), ptr(dq), ptr(dk), ptr(dv), 0, 0, _lib.stream(q.device),
+             work=("mfma", 5 * 2 * N * M * D * B * H))  # (padded shapes, as above)
+        return dq, dk, dv, None, None
+
+
 def attention_bwd_work(B: int, D: int, H: int, N: int, M: int, device) -> Optional[torch.Tensor]:
     """Scratch of pk_attention_bwd (the dQ partials of key blocks 1 ..; None when one block covers M)."""
     nbytes = int(_lib.lib().pk_attention_bwd_work_size(B, D, H, N, M))
     return torch.empty((nbytes // 4,), dtype=torch.float32, device=device) if nbytes > 0 else None
 
 
-def attention(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor) -> torch.Tensor:
+def attention(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, qlen=None, klen=None) -> torch.Tensor:
     """softmax(q^T k / sqrt(d)) v for [B, d, heads, N] fp32 tensors (modeling/dpfm.py:29-37),
-    fused in HIP (pk_attention_fwd/_bwd); the score matrix never reaches HBM."""
+    fused in HIP (pk_attention_fwd/_bwd); the score matrix never reaches HBM.
+    qlen / klen (masked mode; int32 [B] on the device, either may be None = full): crop b's real
+    queries / keys. Keys past klen[b] take no part in the softmax; rows past qlen[b] of the result
+    (and of every gradient, past the respective length) are 0."""
     if query.shape[1] != 16:
         raise _lib.PoseKernError("attention kernel is built for dim = 16 (gnn_dim 32, 2 heads)")
     if query.dtype != torch.float32:
         raise _lib.PoseKernError("attention kernel computes in fp32")
-    return _Attention.apply(query, key, value)
+    if qlen is None and klen is None:
+        return _Attention.apply(query, key, value)
+    B = query.shape[0]
+    return _AttentionVarlen.apply(query, key, value, _lens(qlen, B, query.device), _lens(klen, B, query.device))
 
 
 # ------------------------------------------------------------------------------ per-point layers
@@ -595,40 +645,86 @@ class _InstNormReLU(torch.autograd.Function):
         return dx, None
 
 
-def instnorm_relu(x: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
+class _InstNormReLUVarlen(torch.autograd.Function):
+    """_InstNormReLU with the statistics over each crop's first lens[b] points (masked mode)."""
+
+    @staticmethod
+    def forward(ctx, x, eps, lens):
+        B, C, N = x.shape
+        y = torch.empty_like(x)
+        mean = torch.empty((B * C,), dtype=torch.float32, device=x.device)
+        invstd = torch.empty_like(mean)
+        call("pk_instnorm_relu_fwd_varlen", ptr(x), B * C, N, float(eps), ptr(y), ptr(mean), ptr(invstd), C,
+             ptr(lens), _lib.stream(x.device), work=("hbm", 8 * B * C * N))  # (padded shape: an upper bound)
+        ctx.save_for_backward(x, mean, invstd, lens)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, invstd, lens = ctx.saved_tensors
+        B, C, N = x.shape
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        call("pk_instnorm_relu_bwd_varlen", ptr(x), ptr(dy), ptr(mean), ptr(invstd), B * C, N, ptr(dx), C, ptr(lens),
+             _lib.stream(x.device), work=("hbm", 12 * B * C * N))
+        return dx, None, None
+
+
+def instnorm_relu(x: torch.Tensor, eps: float = 1e-5, lens=None) -> torch.Tensor:
     """relu(InstanceNorm1d(C, affine=False, eps)(x)) for channels-first f32 x [B, C, N], fused
-    forward and backward (pk_instnorm_relu_fwd/_bwd)."""
+    forward and backward (pk_instnorm_relu_fwd/_bwd). lens (masked mode; int32 [B] on the device):
+    the statistics are over crop b's first lens[b] points; the result and its gradient are 0 past
+    them."""
     if x.dim() != 3 or x.dtype != torch.float32:
         raise _lib.PoseKernError("instnorm_relu takes f32 [B, C, N]")
-    return _InstNormReLU.apply(x.contiguous(), eps)
+    if lens is None:
+        return _InstNormReLU.apply(x.contiguous(), eps)
+    return _InstNormReLUVarlen.apply(x.contiguous(), eps, _lens(lens, x.shape[0], x.device))
+
+
+def _wbce_call(p12, t12, p21, t21, n1, n2, loss, g12, g21) -> None:
+    """pk_wbce, or pk_wbce_varlen when either true count is given (masked mode)."""
+    B, N1 = p12.shape
+    N2 = p21.shape[1]
+    if n1 is None and n2 is None:
+        call("pk_wbce", ptr(p12), ptr(t12), N1, ptr(p21), ptr(t21), N2, B, ptr(loss), ptr(g12), ptr(g21),
+             _lib.stream(p12.device), work=None)
+    else:
+        call("pk_wbce_varlen", ptr(p12), ptr(t12), N1, ptr(p21), ptr(t21), N2, B, ptr(n1), ptr(n2), ptr(loss),
+             ptr(g12), ptr(g21), _lib.stream(p12.device), work=None)
 
 
 class _WBCE(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, p12, p21, t12, t21, want):
-        B, N1 = p12.shape
-        N2 = p21.shape[1]
+    def forward(ctx, p12, p21, t12, t21, want, n1=None, n2=None):
+        B = p12.shape[0]
         loss = torch.empty((2, B), dtype=torch.float32, device=p12.device)
         g12 = torch.empty_like(p12) if want else None
         g21 = torch.empty_like(p21) if want else None
-        call("pk_wbce", ptr(p12), ptr(t12), N1, ptr(p21), ptr(t21), N2, B, ptr(loss), ptr(g12), ptr(g21),
-             _lib.stream(p12.device), work=None)
+        _wbce_call(p12, t12, p21, t21, n1, n2, loss, g12, g21)
         ctx.save_for_backward(g12, g21)
         return loss
 
     @staticmethod
     def backward(ctx, gl):
         g12, g21 = ctx.saved_tensors
-        return g12 * gl[0][:, None], g21 * gl[1][:, None], None, None, None
+        return g12 * gl[0][:, None], g21 * gl[1][:, None], None, None, None, None, None
 
 
-def weighted_bce_pair(p12: torch.Tensor, p21: torch.Tensor, t12: torch.Tensor, t21: torch.Tensor) -> torch.Tensor:
+def weighted_bce_pair(p12: torch.Tensor, p21: torch.Tensor, t12: torch.Tensor, t21: torch.Tensor,
+                      n1=None, n2=None) -> torch.Tensor:
     """Upstream WeightedBCELoss for both overlap directions of every crop (pk_wbce): p f32
-    [B, N], t 0/1 masks [B, N] -> loss f32 [2, B] (row 0: p12, row 1: p21)."""
+    [B, N], t 0/1 masks [B, N] -> loss f32 [2, B] (row 0: p12, row 1: p21). n1 / n2 (masked mode;
+    int32 [B] on the device): the true counts of the p12 / p21 rows — class weight, mean and
+    gradient use them, and the gradient is 0 past them."""
     def mask(t):
         return (t if t.dtype == torch.int8 else (t >= 0.5).to(torch.int8)).contiguous()
     want = torch.is_grad_enabled() and (p12.requires_grad or p21.requires_grad)
-    return _WBCE.apply(p12.contiguous(), p21.contiguous(), mask(t12), mask(t21), want)
+    if n1 is None and n2 is None:
+        return _WBCE.apply(p12.contiguous(), p21.contiguous(), mask(t12), mask(t21), want)
+    B, dev = p12.shape[0], p12.device
+    return _WBCE.apply(p12.contiguous(), p21.contiguous(), mask(t12), mask(t21), want, _lens(n1, B, dev),
+                       _lens(n2, B, dev))
 
 
 def _l2_layout(x: torch.Tensor):
@@ -1154,18 +1250,16 @@ class _DPFMLossFn(torch.autograd.Function):
     weights, sums, dloss/dC12); the backward is one grouped scale (pk_loss_scale)."""
 
     @staticmethod
-    def forward(ctx, C12, f1, f2, o12, o21, C_gt, pairs, rows, valid, t12, t21, w, nce_t, prenorm):
+    def forward(ctx, C12, f1, f2, o12, o21, C_gt, pairs, rows, valid, t12, t21, w, nce_t, prenorm, n1=None, n2=None):
         w_fmap, w_acc, w_nce = w
         want = any(ctx.needs_input_grad[:5])
         B, K = C12.shape[0], C12.shape[1]
         dev = C12.device
         nce, g1, g2 = _nce_raw(f1, f2, pairs, rows, valid, nce_t, want, prenorm)
-        N1, N2 = o12.shape[1], o21.shape[1]
         wb = torch.empty((2, B), dtype=torch.float32, device=dev)
         g12 = torch.empty_like(o12) if want else None
         g21 = torch.empty_like(o21) if want else None
-        call("pk_wbce", ptr(o12), ptr(t12), N1, ptr(o21), ptr(t21), N2, B, ptr(wb), ptr(g12), ptr(g21),
-             _lib.stream(dev), work=None)
+        _wbce_call(o12, t12, o21, t21, n1, n2, wb, g12, g21)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         logs = torch.empty((3,), dtype=torch.float32, device=dev)
         dC = torch.empty_like(C12)
@@ -1182,7 +1276,7 @@ class _DPFMLossFn(torch.autograd.Function):
         import ctypes
         saved = ctx.saved_tensors
         if gl is None:  # (not materialised: nothing flows into the loss)
-            return (None,) * 14
+            return (None,) * 16
         need = ctx.needs_input_grad[:5]
         outs = [torch.empty_like(t) if (n and t is not None) else None for t, n in zip(saved, need)]
         sel = [i for i, o in enumerate(outs) if o is not None]
@@ -1192,12 +1286,14 @@ class _DPFMLossFn(torch.autograd.Function):
                  (ctypes.c_int64 * len(sel))(*[saved[i].numel() for i in sel]),
                  (ctypes.c_float * len(sel))(*[ctx.scales[i] for i in sel]), len(sel), ptr(gl.contiguous()),
                  _lib.stream(gl.device), work=None)
-        return (*outs, None, None, None, None, None, None, None, None, None)
+        return (*outs, None, None, None, None, None, None, None, None, None, None, None)
 
 
 def dpfm_loss(C12, C_gt, f1, f2, pairs, rows, valid, o12, o21, t12, t21, w_fmap: float, w_acc: float,
-              w_nce: float, nce_t: float):
-    """DPFMLoss.forward for every crop at once -> (loss 0-d, logs f32 [3] = nce, acc, fmap)."""
+              w_nce: float, nce_t: float, n1=None, n2=None):
+    """DPFMLoss.forward for every crop at once -> (loss 0-d, logs f32 [3] = nce, acc, fmap).
+    n1 / n2 (masked mode; int32 [B] on the device): the crops' true point counts for the WBCE
+    term (pk_wbce_varlen); the other terms do not see padding."""
     def mask(t):
         return (t if t.dtype == torch.int8 else (t >= 0.5).to(torch.int8)).contiguous()
     if f1.dtype != torch.float32 or f1.shape[-1] != 32:
@@ -1205,10 +1301,16 @@ def dpfm_loss(C12, C_gt, f1, f2, pairs, rows, valid, o12, o21, t12, t21, w_fmap:
     # features whose F.normalize'd rows copy the overlap head already made (l2_normalize_two):
     # the NCE term reads those rows (coalesced) and its gradient joins the overlap head's in
     # the one l2-normalize backward
-    n1, n2 = getattr(f1, "_pk_nrows", None), getattr(f2, "_pk_nrows", None)
-    prenorm = n1 is not None and n2 is not None
+    nr1, nr2 = getattr(f1, "_pk_nrows", None), getattr(f2, "_pk_nrows", None)
+    prenorm = nr1 is not None and nr2 is not None
     if prenorm:
-        f1, f2 = n1, n2
+        f1, f2 = nr1, nr2
+    if n1 is not None or n2 is not None:
+        B, dev = C12.shape[0], C12.device
+        return _DPFMLossFn.apply(C12.contiguous(), f1, f2, o12.contiguous(), o21.contiguous(), C_gt.contiguous(),
+                                 pairs.contiguous(), rows.contiguous(), valid.contiguous().view(torch.uint8),
+                                 mask(t12), mask(t21), (float(w_fmap), float(w_acc), float(w_nce)), float(nce_t),
+                                 bool(prenorm), _lens(n1, B, dev), _lens(n2, B, dev))
     return _DPFMLossFn.apply(C12.contiguous(), f1, f2, o12.contiguous(), o21.contiguous(), C_gt.contiguous(),
                              pairs.contiguous(), rows.contiguous(), valid.contiguous().view(torch.uint8),
                              mask(t12), mask(t21), (float(w_fmap), float(w_acc), float(w_nce)), float(nce_t),

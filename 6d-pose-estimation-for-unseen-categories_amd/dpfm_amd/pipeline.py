@@ -187,12 +187,18 @@ def operators_for(cads: list, crop_counts: list, diam: list, seed: int, device, 
                      cad_n=torch.tensor([len(c) for c in cads], dtype=torch.int32, device=d))
 
 
-def model_batch(op: Operators, crops: Crops) -> dict:
-    """The {"shape1": CAD, "shape2": PC} dict of train.py:88-91 (L/grad operators None)."""
+def model_batch(op: Operators, crops: Crops, masked: bool = False) -> dict:
+    """The {"shape1": CAD, "shape2": PC} dict of train.py:88-91 (L/grad operators None).
+    masked: each shape also carries "n", its crops' true point counts (op.cad_n / crops.n2, int32
+    [B] on the device; absent counts mean full length) for DPFMNet(masked=True)."""
     cad = {"xyz": op.cad_xyz, "mass": op.cad_mass, "evals": op.cad_evals, "evecs": op.cad_evecs,
            "L": None, "gradX": None, "gradY": None, "faces": None}
     pc = {"xyz": crops.pc32, "mass": op.pc_mass, "evals": op.pc_evals, "evecs": op.pc_evecs,
           "L": None, "gradX": None, "gradY": None}
+    if masked:
+        B, dev = op.cad_xyz.shape[0], op.cad_xyz.device
+        cad["n"] = _counts(op.cad_n, B, op.cad_xyz.shape[1], dev)
+        pc["n"] = _counts(crops.n2, B, crops.pc32.shape[1], dev)
     return {"shape1": cad, "shape2": pc}
 
 
@@ -226,8 +232,13 @@ class TrainStep:
 
     def __init__(self, model: DPFMNet, lr: float = 5e-4, max_norm: float = 5.0, nce_num_pairs: int = 512,
                  group: Optional[dist.ProcessGroup] = None, seed: int = 0, capturable: bool = False,
-                 grouped: bool = True, fused_opt: bool = True):
+                 grouped: bool = True, fused_opt: bool = True, masked: bool = False):
         self.model = model
+        # masked mode: the true crop lengths go to the model (which must be DPFMNet(masked=True))
+        # and to the loss's WBCE term; they stay on the device (capturable like the rest)
+        self.masked = bool(masked)
+        if self.masked != bool(getattr(model, "masked", False)):
+            raise ValueError("TrainStep(masked=...) must match the model's DPFMNet(masked=...)")
         self.params = [p for p in model.parameters()]
         # config/dpfm_orig.gin:62-63; capturable keeps the step count on the device
         self.opt = torch.optim.RMSprop(self.params, lr=lr, capturable=capturable)
@@ -339,14 +350,15 @@ class TrainStep:
         """ir=False leaves the naive point map + IR out of the step (PipelinedTrainer computes it
         beside the next steps from the C_pred this step leaves in `self.last_C_pred`)."""
         self.model.train()
-        batch = model_batch(op, crops)
+        batch = model_batch(op, crops, self.masked)
         C_gt = crops.C_gt
         if C_gt is None:
             C_gt = self.ground_truth(op, crops)
         C_pred, o12, o21, f1, f2, _, _ = self.model(batch)
         self.last_C_pred = C_pred.detach()
         loss, log = self.crit.forward_batched(C_pred, C_gt, crops.pairs, crops.npairs, f1, f2, o12, o21,
-                                              crops.overlap_12, crops.overlap_21, generator=self.gen)
+                                              crops.overlap_12, crops.overlap_21, generator=self.gen,
+                                              n1=batch["shape1"].get("n"), n2=batch["shape2"].get("n"))
         with torch.no_grad():  # train.py:109-116 (naive solver + IR per crop)
             st = torch.empty((C_pred.shape[0],), dtype=torch.int32, device=C_pred.device) if ir else None
             ir = self.inlier_ratio_of(op, crops, C_pred, status=st) if ir else None
@@ -663,13 +675,16 @@ class InferStep:
     """eval.py inference + test_RANSAC.py pose fit for a batch of crops."""
 
     def __init__(self, model: DPFMNet, hypotheses: int = 1024, seed: int = 0, max_dist: float = 0.05,
-                 icp_evaluations: int = 0, icp_threshold: float = 0.2):
+                 icp_evaluations: int = 0, icp_threshold: float = 0.2, masked: bool = False):
         """icp_evaluations > 0 refines each RANSAC pose by point-to-point ICP of the CAD against the
         observed crop (test_RANSAC.py:436-446 runs ICP after RANSAC, against the GT-posed CAD; the
         crop is the target available without ground truth), with that many evaluations enqueued
         (capturable: no host read) and the metrics also reported for the refined pose."""
         self.model, self.H, self.seed, self.max_dist = model, hypotheses, seed, max_dist
         self.icp_evaluations, self.icp_threshold = icp_evaluations, icp_threshold
+        self.masked = bool(masked)  # the model then reads the crops' true lengths (DPFMNet(masked=True))
+        if self.masked != bool(getattr(model, "masked", False)):
+            raise ValueError("InferStep(masked=...) must match the model's DPFMNet(masked=...)")
 
     @torch.no_grad()
     def __call__(self, fb: FrameBatch, op: Operators, crops: Crops):
@@ -680,7 +695,7 @@ class InferStep:
         """DPFMNet forward and the naive solver's top-5 candidates (eval.py:80-87,
         spacial_filtering.py:32-38): the MFMA-bound first half of the step."""
         self.model.eval()
-        C_pred, o12, o21, f1, f2, _, _ = self.model(model_batch(op, crops))
+        C_pred, o12, o21, f1, f2, _, _ = self.model(model_batch(op, crops, self.masked))
         B, V1, _ = op.cad_evecs.shape
         V2 = op.pc_evecs.shape[1]
         dev = C_pred.device

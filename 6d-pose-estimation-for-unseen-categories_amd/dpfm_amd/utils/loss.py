@@ -109,10 +109,12 @@ class DPFMLoss(nn.Module):
         self.nce_softmax_loss = NCESoftmaxLoss(nce_t, nce_num_pairs)
 
     def forward_batched(self, C12, C_gt, pairs, npairs, feat1, feat2, o12, o21, gt12, gt21,
-                        generator: Optional[torch.Generator] = None, selection=None):
+                        generator: Optional[torch.Generator] = None, selection=None, n1=None, n2=None):
         """All crops at once. pairs int64 [B, cap, 2] (CAD idx, PC idx), npairs [B];
         returns (loss, dict of 0-d tensors). One autograd node (ops.dpfm_loss): the NCE and
-        WBCE kernels with their input gradients plus the fused scalar head."""
+        WBCE kernels with their input gradients plus the fused scalar head.
+        n1 / n2 (masked mode; int32 [B] on the device): the crops' true point counts — the WBCE
+        term then leaves the padding out of its class weights and mean."""
         from .. import ops
         if not C12.is_cuda:
             raise ops._lib.PoseKernError("DPFMLoss runs on HIP devices only (no CPU fallback)")
@@ -121,11 +123,11 @@ class DPFMLoss(nn.Module):
         rows, valid = selection if selection is not None else nce_select(
             npairs, pairs.shape[1], self.nce_softmax_loss.nce_num_pairs, generator)
         loss, logs = ops.dpfm_loss(C12, C_gt, feat1, feat2, pairs, rows, valid, o12, o21, gt12, gt21,
-                                   self.w_fmap, self.w_acc, self.w_nce, self.nce_softmax_loss.nce_t)
+                                   self.w_fmap, self.w_acc, self.w_nce, self.nce_softmax_loss.nce_t, n1=n1, n2=n2)
         return loss, {"nce_loss": logs[0], "acc_loss": logs[1], "fmap_loss": logs[2], "loss": loss.detach()}
 
     def forward_batched_composed(self, C12, C_gt, pairs, npairs, feat1, feat2, o12, o21, gt12, gt21,
-                                 generator: Optional[torch.Generator] = None, selection=None):
+                                 generator: Optional[torch.Generator] = None, selection=None, n1=None, n2=None):
         """The same loss composed from the per-term kernels and torch ops (development
         comparison for the fused head)."""
         fmap_loss = self.frob_loss(C12, C_gt) * self.w_fmap
@@ -137,7 +139,7 @@ class DPFMLoss(nn.Module):
         nce = self.nce_softmax_loss.forward_batched(feat1, feat2, pairs, rows, valid)
         nce_loss = (nce * self.w_nce / m).sum()
         from .. import ops
-        wb = ops.weighted_bce_pair(o12, o21, gt12, gt21)  # both directions, loss + gradient, one launch
+        wb = ops.weighted_bce_pair(o12, o21, gt12, gt21, n1=n1, n2=n2)  # both directions, loss + gradient, one launch
         acc_loss = ((wb[0] + wb[1]) * self.w_acc / m).sum()
         loss = fmap_loss + acc_loss + nce_loss
         return loss, {"nce_loss": nce_loss.detach(), "acc_loss": acc_loss.detach(),

@@ -185,6 +185,23 @@ int pk_attention_bwd(const float* q, const float* k, const float* v, const float
                      const float* dout, const float* lse, int B, int D, int H, int N, int M,
                      int64_t sbk, int64_t sbv, float* work, float* dq, float* dk, float* dv, int64_t sbdk,
                      int64_t sbdv, void* stream);
+/* Masked mode of the same attention (modeling/dpfm.py:29-37 applied to each crop's real points
+ * only; the reference itself attends to collate's zero padding, dataset/helpers.py:22-50 — a
+ * build-defined deviation). qlen / klen: device int32 [B], the real queries /
+ * keys of crop b (clamped to [0, N] / [0, M]; NULL = all), read on the device: no host sync. N and
+ * M stay the addressing strides. Crop b's real rows equal pk_attention_fwd / _bwd run on that crop
+ * alone, unpadded. Forward: rows n >= qlen[b] of out are 0 and of lse (0, 0); klen[b] == 0 gives
+ * out = 0, lse = (0, 0) for the crop. Backward: dq rows >= qlen[b] and dk / dv rows >= klen[b] are
+ * written as 0; rows >= qlen[b] of dout / out / lse are not used. Nothing at an index >= qlen[b] of
+ * q or >= klen[b] of k / v influences any output. work as pk_attention_bwd_work_size(B, D, H, N, M)
+ * (any contents); the second launch always runs and adds only the partial slots of live key blocks. */
+int pk_attention_fwd_varlen(const float* q, const float* k, const float* v, int B, int D, int H, int N,
+                            int M, int64_t sbk, int64_t sbv, const int* qlen, const int* klen, float* out,
+                            float* lse, void* stream);
+int pk_attention_bwd_varlen(const float* q, const float* k, const float* v, const float* out,
+                            const float* dout, const float* lse, int B, int D, int H, int N, int M,
+                            int64_t sbk, int64_t sbv, const int* qlen, const int* klen, float* work, float* dq,
+                            float* dk, float* dv, int64_t sbdk, int64_t sbdv, void* stream);
 
 /* Weight/bias gradients of the per-point layers of H7/H8 (DiffusionNet Linear layers,
  * models/dpfm.py:22-30; refinement Conv1d(k=1), modeling/dpfm.py:16-26,45-54,82-95):
@@ -239,6 +256,16 @@ int pk_instnorm_relu_fwd(const float* x, int64_t rows, int N, float eps, float* 
                          void* stream);
 int pk_instnorm_relu_bwd(const float* x, const float* dy, const float* mean, const float* invstd, int64_t rows,
                          int N, float* dx, void* stream);
+/* Masked mode of the same layer (modeling/dpfm.py:16-26's InstanceNorm1d over each crop's real
+ * points only; the reference's statistics include collate's padding — a build-defined deviation,
+ * SURVEY Appendix B #1). Row r belongs to crop r / C; lens: device int32 [rows / C] (clamped to
+ * [0, N]; NULL = N). Mean, biased variance and the backward's two means are over the first
+ * n = lens[r / C] points and divided by n; y and dx are 0 at points >= n, which are not loaded.
+ * n == 0: mean = 0, invstd = 1 / sqrt(eps), outputs 0. */
+int pk_instnorm_relu_fwd_varlen(const float* x, int64_t rows, int N, float eps, float* y, float* mean,
+                                float* invstd, int C, const int* lens, void* stream);
+int pk_instnorm_relu_bwd_varlen(const float* x, const float* dy, const float* mean, const float* invstd,
+                                int64_t rows, int N, float* dx, int C, const int* lens, void* stream);
 
 /* H15 overlap term: upstream WeightedBCELoss (utils/loss.py:79-83) for both directions of
  * B crops in one launch. p12 f32 [B, N1] / p21 [B, N2] sigmoid outputs, t12 / t21 int8 0/1
@@ -246,6 +273,13 @@ int pk_instnorm_relu_bwd(const float* x, const float* dy, const float* mean, con
  * d loss[., b] / d p. */
 int pk_wbce(const float* p12, const int8_t* t12, int N1, const float* p21, const int8_t* t21, int N2, int B,
             float* loss, float* g12, float* g21, void* stream);
+/* Masked mode of the same term (utils/loss.py:79-83 on each crop's real points only; the
+ * reference's masks are padded by collate — a build-defined deviation).
+ * n1 / n2: device int32 [B] true counts of the p12 / p21 rows (clamped to [0, N1] / [0, N2]; NULL =
+ * all). The class weight, the mean and the gradient's 1 / N use the true count; gradients past it
+ * are 0; an empty crop's loss is 0. N1 / N2 stay the row strides. */
+int pk_wbce_varlen(const float* p12, const int8_t* t12, int N1, const float* p21, const int8_t* t21, int N2,
+                   int B, const int* n1, const int* n2, float* loss, float* g12, float* g21, void* stream);
 
 /* models/dpfm.py:53,61-66: out = cat((a - sub) * mul, (b - sub) * mul) over na + nb f32
  * elements (the shared encoder's input features; mul = float32(1) / 50, the reciprocal torch
