@@ -114,6 +114,11 @@ SIGNATURES = {
     "pk_icp_iterate": [_P, _P, _P, _P, _D, _I, _D, _D, _I, _I, _I, _I, _P, _I64, _P, _P],
     "pk_icp_result": [_P, _I, _P, _P, _P],
     "pk_icp": [_P, _P, _P, _P, _P, _D, _I, _D, _D, _I, _I, _I, _I, _P, _I64, _P, _P, _P, _P],
+    "pk_normals_work_size": [_I, _I],
+    "pk_estimate_normals": [_P, _P, _I, _I, _I, _D, _D, _D, _P, _P, _P, _I64, _P],
+    "pk_icp_plane_work_size": [_I, _I, _I],
+    "pk_icp_plane_init": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I64, _P],
+    "pk_icp_plane_iterate": [_P, _P, _P, _P, _D, _I, _D, _D, _I, _I, _I, _I, _P, _I64, _P, _P],
     "pk_teaser_graph": [_P, _P, _P, _I, _I, _D, _P, _P, _P],
     "pk_knn": [_P, _P, _I, _I, _I, _I, _P, _P, _P],
     "pk_pc_local_tri": [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P],
@@ -137,7 +142,8 @@ SIGNATURES = {
 
 RESTYPES = {"pk_cgt_lstsq_work_size": _I64, "pk_linear_wgrad_grouped_work": _I64, "pk_ransac_work_size": _I64,
             "pk_feat_dist_work_size": _I64, "pk_fmap_head_work_len": _I64, "pk_icp_work_size": _I64,
-            "pk_rigidity_filter_work_size": _I64, "pk_attention_bwd_work_size": _I64}  # everything else returns an int status
+            "pk_rigidity_filter_work_size": _I64, "pk_attention_bwd_work_size": _I64,
+            "pk_normals_work_size": _I64, "pk_icp_plane_work_size": _I64}  # everything else returns an int status
 
 _lib: Optional[ctypes.CDLL] = None
 _dev_lib: Optional[ctypes.CDLL] = None

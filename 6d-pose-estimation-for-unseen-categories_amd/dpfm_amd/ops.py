@@ -1423,10 +1423,62 @@ def ransac(src: torch.Tensor, src_off: torch.Tensor, dst: torch.Tensor, dst_off:
     return T, stats
 
 
+ICP_ESTIMATIONS = ("point_to_point", "point_to_plane")
+
+
+def estimate_normals(points: torch.Tensor, off: torch.Tensor, k: int = 30, viewpoint=None,
+                     nmax: Optional[int] = None, return_knn: bool = False):
+    """pk_estimate_normals: Open3D estimate_normals(KDTreeSearchParamKNN(k)) oriented towards
+    `viewpoint` (3 numbers; the origin if None) for packed crops (points f64 [T,3], off int64
+    [B+1]) -> normals f64 [T,3] (and the neighbour indices int32 [T,k], crop-local, -1 past the
+    crop's size). No host read when nmax (the largest crop's capacity) is given; a crop above it
+    gets NaN normals."""
+    if not 3 <= int(k) <= 32:
+        raise ValueError(f"estimate_normals: k must be in [3, 32], got {k}")
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float64:
+        raise ValueError("estimate_normals: points must be f64 [T,3]")
+    vp = (0.0, 0.0, 0.0) if viewpoint is None else tuple(float(v) for v in viewpoint)
+    if len(vp) != 3:
+        raise ValueError("estimate_normals: viewpoint must have 3 components")
+    B = off.numel() - 1
+    dev = points.device
+    if nmax is None:
+        nmax = int((off[1:] - off[:-1]).max()) if B else 0
+    N = int(points.shape[0])
+    normals = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    knn = torch.empty((N, int(k)), dtype=torch.int32, device=dev) if return_knn else None
+    nbytes = int(_lib.lib().pk_normals_work_size(B, int(nmax)))
+    work = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+    if B and N:
+        call("pk_estimate_normals", ptr(points), ptr(off), B, int(nmax), int(k), vp[0], vp[1], vp[2], ptr(normals),
+             ptr(knn), ptr(work), nbytes, _lib.stream(dev), work=("valu64", N * int(k) * 400))
+    return (normals, knn) if return_knn else normals
+
+
+def _icp_entry(estimation: str, tgt: torch.Tensor, tgt_off: torch.Tensor, tgt_normals, normals_k: int, ntgt_max: int):
+    """The entry points of an estimator and, for point_to_plane, the target normals (estimated
+    from the target with the viewpoint at the origin when the caller passes none)."""
+    if estimation not in ICP_ESTIMATIONS:
+        raise ValueError(f"icp: estimation must be one of {ICP_ESTIMATIONS}, got {estimation!r}")
+    if estimation == "point_to_point":
+        if tgt_normals is not None:
+            raise ValueError("icp: tgt_normals are read by estimation='point_to_plane' only")
+        return "pk_icp_work_size", "pk_icp_init", "pk_icp_iterate", None
+    if tgt_normals is None:
+        tgt_normals = estimate_normals(tgt, tgt_off, k=normals_k, nmax=ntgt_max)
+    elif tuple(tgt_normals.shape) != tuple(tgt.shape) or tgt_normals.dtype != torch.float64:
+        raise ValueError(f"icp: tgt_normals must be f64 {tuple(tgt.shape)} like the target, got "
+                         f"{tgt_normals.dtype} {tuple(tgt_normals.shape)}")
+    return "pk_icp_plane_work_size", "pk_icp_plane_init", "pk_icp_plane_iterate", tgt_normals.contiguous()
+
+
 def icp(src: torch.Tensor, src_off: torch.Tensor, tgt: torch.Tensor, tgt_off: torch.Tensor, T_init: torch.Tensor,
         max_dist: float, max_iter: int = 30, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6,
-        nsrc_max: Optional[int] = None, ntgt_max: Optional[int] = None, poll: int = 8):
-    """Batched point-to-point ICP (pk_icp_init / pk_icp_iterate / pk_icp_result). Iterations are
+        nsrc_max: Optional[int] = None, ntgt_max: Optional[int] = None, poll: int = 8,
+        estimation: str = "point_to_point", tgt_normals: Optional[torch.Tensor] = None, normals_k: int = 30):
+    """Batched ICP (pk_icp_init / pk_icp_iterate / pk_icp_result, or pk_icp_plane_* with
+    estimation="point_to_plane": tgt_normals f64 like tgt, estimated from the target with
+    normals_k neighbours if None). Iterations are
     enqueued `poll` at a time; between batches the host reads the device count of crops still
     iterating (one 4-byte read). Returns (T f64 [B,4,4], stats f64 [B,4] = fitness, inlier rmse,
     updates, converged)."""
@@ -1436,17 +1488,19 @@ def icp(src: torch.Tensor, src_off: torch.Tensor, tgt: torch.Tensor, tgt_off: to
         nsrc_max = int((src_off[1:] - src_off[:-1]).max()) if B else 0
     if ntgt_max is None:
         ntgt_max = int((tgt_off[1:] - tgt_off[:-1]).max()) if B else 0
+    f_size, f_init, f_iter, normals = _icp_entry(estimation, tgt, tgt_off, tgt_normals, normals_k, int(ntgt_max))
+    nrm = () if normals is None else (ptr(normals),)
     T0 = T_init.to(dtype=torch.float64).reshape(B, 16).contiguous()
-    nbytes = int(_lib.lib().pk_icp_work_size(B, int(nsrc_max), int(ntgt_max)))
+    nbytes = int(getattr(_lib.lib(), f_size)(B, int(nsrc_max), int(ntgt_max)))
     work = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
     cnt = torch.zeros((1,), dtype=torch.int32, device=dev)
     s = _lib.stream(dev)
-    call("pk_icp_init", ptr(src), ptr(src_off), ptr(tgt), ptr(tgt_off), ptr(T0), B, int(nsrc_max), int(ntgt_max),
+    call(f_init, ptr(src), ptr(src_off), ptr(tgt), ptr(tgt_off), *nrm, ptr(T0), B, int(nsrc_max), int(ntgt_max),
          ptr(work), nbytes, s)
     done = 0
     while B and done <= max_iter:
         steps = min(int(poll), max_iter + 1 - done)
-        call("pk_icp_iterate", ptr(src), ptr(src_off), ptr(tgt), ptr(tgt_off), float(max_dist), int(max_iter),
+        call(f_iter, ptr(src), ptr(src_off), ptr(tgt), ptr(tgt_off), float(max_dist), int(max_iter),
              float(rel_fitness), float(rel_rmse), B, int(nsrc_max), int(ntgt_max), steps, ptr(work), nbytes,
              ptr(cnt), s, work=("hbm", steps * int(src.shape[0]) * 48))  # upper bound: source + matched target rows
         done += steps
@@ -1617,19 +1671,22 @@ def dpotrs(L: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
 
 def icp_fixed(src: torch.Tensor, src_off: torch.Tensor, tgt: torch.Tensor, tgt_off: torch.Tensor,
               T_init: torch.Tensor, max_dist: float, evaluations: int, nsrc_max: int, ntgt_max: int,
-              rel_fitness: float = 1e-6, rel_rmse: float = 1e-6):
+              rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, estimation: str = "point_to_point",
+              tgt_normals: Optional[torch.Tensor] = None, normals_k: int = 30):
     """ICP with a fixed number of enqueued evaluations and no host read (HIP-graph capturable):
     max_iteration = evaluations - 1, so every crop stops by the last one (converged crops return
-    early in each launch). Same results as `icp` with that max_iteration."""
+    early in each launch). Same results as `icp` with that max_iteration (and that estimation)."""
     B = src_off.numel() - 1
     dev = src.device
+    f_size, f_init, f_iter, normals = _icp_entry(estimation, tgt, tgt_off, tgt_normals, normals_k, int(ntgt_max))
+    nrm = () if normals is None else (ptr(normals),)
     T0 = T_init.to(dtype=torch.float64).reshape(B, 16).contiguous()
-    nbytes = int(_lib.lib().pk_icp_work_size(B, int(nsrc_max), int(ntgt_max)))
+    nbytes = int(getattr(_lib.lib(), f_size)(B, int(nsrc_max), int(ntgt_max)))
     work = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
     s = _lib.stream(dev)
-    call("pk_icp_init", ptr(src), ptr(src_off), ptr(tgt), ptr(tgt_off), ptr(T0), B, int(nsrc_max), int(ntgt_max),
+    call(f_init, ptr(src), ptr(src_off), ptr(tgt), ptr(tgt_off), *nrm, ptr(T0), B, int(nsrc_max), int(ntgt_max),
          ptr(work), nbytes, s)
-    call("pk_icp_iterate", ptr(src), ptr(src_off), ptr(tgt), ptr(tgt_off), float(max_dist), int(evaluations) - 1,
+    call(f_iter, ptr(src), ptr(src_off), ptr(tgt), ptr(tgt_off), float(max_dist), int(evaluations) - 1,
          float(rel_fitness), float(rel_rmse), B, int(nsrc_max), int(ntgt_max), int(evaluations), ptr(work), nbytes,
          None, s, work=("hbm", int(evaluations) * int(src.shape[0]) * 48))
     T = torch.empty((B, 4, 4), dtype=torch.float64, device=dev)

@@ -675,13 +675,20 @@ class InferStep:
     """eval.py inference + test_RANSAC.py pose fit for a batch of crops."""
 
     def __init__(self, model: DPFMNet, hypotheses: int = 1024, seed: int = 0, max_dist: float = 0.05,
-                 icp_evaluations: int = 0, icp_threshold: float = 0.2, masked: bool = False):
+                 icp_evaluations: int = 0, icp_threshold: float = 0.2, masked: bool = False,
+                 icp_estimation: str = "point_to_point"):
         """icp_evaluations > 0 refines each RANSAC pose by point-to-point ICP of the CAD against the
         observed crop (test_RANSAC.py:436-446 runs ICP after RANSAC, against the GT-posed CAD; the
         crop is the target available without ground truth), with that many evaluations enqueued
-        (capturable: no host read) and the metrics also reported for the refined pose."""
+        (capturable: no host read) and the metrics also reported for the refined pose.
+        icp_estimation="point_to_plane": the crop's normals are estimated inside the step (30
+        neighbours, oriented towards the camera at the origin) and the ICP update is Open3D's
+        TransformationEstimationPointToPlane."""
+        if icp_estimation not in ops.ICP_ESTIMATIONS:
+            raise ValueError(f"icp_estimation must be one of {ops.ICP_ESTIMATIONS}, got {icp_estimation!r}")
         self.model, self.H, self.seed, self.max_dist = model, hypotheses, seed, max_dist
         self.icp_evaluations, self.icp_threshold = icp_evaluations, icp_threshold
+        self.icp_estimation = icp_estimation
         self.masked = bool(masked)  # the model then reads the crops' true lengths (DPFMNet(masked=True))
         if self.masked != bool(getattr(model, "masked", False)):
             raise ValueError("InferStep(masked=...) must match the model's DPFMNet(masked=...)")
@@ -746,7 +753,8 @@ class InferStep:
                    corres=corres, cor_off=cor_off, index_status=st_ir | st_rs)
         if self.icp_evaluations > 0:
             T_icp, icp_stats = ops.icp_fixed(fb.cad64, fb.cad_off, crops.pc64, crops.off, T, self.icp_threshold,
-                                             self.icp_evaluations, n1cap, max(int(crops.ld), V2))
+                                             self.icp_evaluations, n1cap, max(int(crops.ld), V2),
+                                             estimation=self.icp_estimation)
             out.update(T_icp=T_icp, icp=icp_stats,
                        metrics_icp=ops.pose_metrics(fb.cad64, fb.cad_off, n1cap, T_icp, T_gt))
         return out

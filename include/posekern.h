@@ -620,6 +620,41 @@ int pk_icp(const double* src, const int64_t* src_off, const double* tgt, const i
            double max_dist, int max_iter, double rel_fitness, double rel_rmse, int B, int nsrc_max, int ntgt_max,
            int poll, void* work, int64_t work_bytes, int32_t* dev_count, double* T, double* stats, void* stream);
 
+/* (f4, opt-in) Normals of a packed point set: Open3D 0.17 PointCloud::EstimateNormals(
+ * KDTreeSearchParamKNN(knn = k)) followed by OrientNormalsTowardsCameraLocation(viewpoint),
+ * restated (parity unpinned: Open3D is absent).
+ *   pts f64 [T,3] packed by off [B+1]; nmax: per-crop capacity (grid and scratch sizing);
+ *   k in [3, 32]; (vx, vy, vz) the viewpoint; normals f64 [T,3]; knn int32 [T,k] or NULL.
+ * Neighbours of a point: its k nearest points of the same crop, itself included, by exact fp64
+ * d^2 = (dx dx + dy dy) + dz dz, ordered by (d^2, index) (ties: lowest index); a crop below k
+ * points uses all of them (knn: crop-local indices, -1 past the crop's size). Covariance: of the
+ * neighbours minus the query point, summed in neighbour order, C = S2 / m - mean mean^T. Normal:
+ * the unit eigenvector of the smallest eigenvalue (cyclic Jacobi), flipped so that
+ * n . (viewpoint - p) >= 0; with fewer than 3 neighbours (0, 0, 1), not flipped. A crop above
+ * nmax is skipped and flagged: its normals are NaN, its knn rows -1. Capture-safe.
+ * work: pk_normals_work_size(B, nmax) bytes (the crops in x order); contents need not survive. */
+int64_t pk_normals_work_size(int B, int nmax);
+int pk_estimate_normals(const double* pts, const int64_t* off, int B, int nmax, int k, double vx, double vy, double vz,
+                        double* normals, int32_t* knn, void* work, int64_t work_bytes, void* stream);
+
+/* (f4, opt-in) Point-to-plane ICP: Open3D 0.17 registration_icp(...,
+ * TransformationEstimationPointToPlane()) restated (parity unpinned). Matching, the pair test,
+ * fitness, the Euclidean inlier rmse, the stop criteria, the flags and T <- U T are those of
+ * pk_icp_*; the update solves the normal equations of the rows J = [p x n, n], r = (p - q) . n
+ * over the pairs (p = T s, q its target point, n = tgt_normals of q; coordinates shifted by the
+ * crop's first target point) by a 6x6 Cholesky factorisation — a non-positive pivot gives U = I —
+ * and U = [Rz(x2) Ry(x1) Rx(x0) | x3..5] (Open3D TransformVector6dToMatrix4d).
+ *   tgt_normals f64 [Tt,3], laid out like tgt (pk_estimate_normals, or the caller's own).
+ * pk_icp_plane_init / pk_icp_plane_iterate take the arguments of pk_icp_init / pk_icp_iterate;
+ * the result is read by pk_icp_result. work: pk_icp_plane_work_size(B, nsrc_max, ntgt_max). */
+int64_t pk_icp_plane_work_size(int B, int nsrc_max, int ntgt_max);
+int pk_icp_plane_init(const double* src, const int64_t* src_off, const double* tgt, const int64_t* tgt_off,
+                      const double* tgt_normals, const double* T_init, int B, int nsrc_max, int ntgt_max, void* work,
+                      int64_t work_bytes, void* stream);
+int pk_icp_plane_iterate(const double* src, const int64_t* src_off, const double* tgt, const int64_t* tgt_off,
+                         double max_dist, int max_iter, double rel_fitness, double rel_rmse, int B, int nsrc_max,
+                         int ntgt_max, int steps, void* work, int64_t work_bytes, int32_t* active_count, void* stream);
+
 /* (f2) TEASER++ robust registration, the alternative pose solver (scripts/test_teaser.py:
  * 327-331, 362-435: RobustRegistrationSolver, cbar2 1, noise_bound 0.05, no scaling, GNC-TLS
  * rotation with gnc factor 1.4 / 100 iterations / cost threshold 1e-12; PMC_EXACT max clique with
