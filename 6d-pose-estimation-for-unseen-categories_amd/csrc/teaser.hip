@@ -20,6 +20,11 @@
 //   4. Translation: per axis, adaptive voting (scalar TLS over the 2m interval endpoints of
 //      b - R a, ranges = noise sqrt(cbar2)) over the clique.
 //
+// With estimate_scaling = true (TEASER's default; csrc/teaser_scale.hip) a step 0 votes the scale
+// s over the TIM ratios of all pairs on the device, step 1's test becomes ||b_j - b_i| / |a_j -
+// a_i| - s| <= 2 noise sqrt(cbar2) / |a_j - a_i|, step 3 divides the crop-side TIMs and the noise
+// bound by s, and step 4 votes over b - s R a (pk_teaser_solve_scaled; T stays the rigid [R | t]).
+//
 // MI355X split: step 1 is the O(n^2) data-parallel part (n = 5 V2 spatial-filter
 // correspondences: 2.6e7 pairs per crop at V2 = 1024) and runs on the device — one workgroup
 // per (crop, row), a wave's 64 column tests packed into one 64-bit adjacency word by a ballot,
@@ -303,8 +308,10 @@ double scalar_tls(const std::vector<double>& X, double range, std::vector<char>*
   return est;
 }
 
+// `scale`: the crop's estimated scale (1 without scale estimation: every product by it is exact,
+// so the unscaled results do not change by a bit).
 void solve_one(const double* a, const double* b, int n, const uint64_t* adj, int W, const int32_t* deg,
-               const pk_teaser_params& p, double* T, int32_t* clique, int32_t* csize, int32_t* info) {
+               const pk_teaser_params& p, double scale, double* T, int32_t* clique, int32_t* csize, int32_t* info) {
   for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.0 : 0.0;
   info[0] = info[1] = info[2] = info[3] = 0;
   *csize = 0;
@@ -326,17 +333,18 @@ void solve_one(const double* a, const double* b, int n, const uint64_t* adj, int
   for (size_t k = 0; k < C.size(); ++k) clique[k] = C[k];
   if (C.size() <= 1) return;  // TEASER: solution invalid
   const int m = (int)C.size();
-  // chain TIMs
+  // chain TIMs, the crop side divided by the scale
+  const double inv_scale = 1.0 / scale;
   std::vector<double> s(3 * m), d(3 * m), w(m, 1.0), r2(m);
   for (int k = 0; k < m; ++k) {
     const int root = C[k], leaf = C[(k + 1) % m];
     for (int c = 0; c < 3; ++c) {
       s[3 * k + c] = a[3 * leaf + c] - a[3 * root + c];
-      d[3 * k + c] = b[3 * leaf + c] - b[3 * root + c];
+      d[3 * k + c] = (b[3 * leaf + c] - b[3 * root + c]) * inv_scale;
     }
   }
-  // GNC-TLS (noise bound 2 noise / scale, scale = 1)
-  double nb2 = std::pow(2.0 * p.noise_bound, 2);
+  // GNC-TLS (noise bound 2 noise / scale)
+  double nb2 = std::pow(2.0 * p.noise_bound / scale, 2);
   if (nb2 < 1e-16) nb2 = 1e-2;
   double R[9], mu = 1.0, prev_cost = std::numeric_limits<double>::infinity();
   for (int it = 0; it < p.rotation_max_iterations; ++it) {
@@ -379,7 +387,7 @@ void solve_one(const double* a, const double* b, int n, const uint64_t* adj, int
     std::vector<double> X(m);
     for (int k = 0; k < m; ++k) {
       const double* ak = a + 3 * C[k];
-      X[k] = b[3 * C[k] + r] - ((R[3 * r] * ak[0] + R[3 * r + 1] * ak[1]) + R[3 * r + 2] * ak[2]);
+      X[k] = b[3 * C[k] + r] - scale * ((R[3 * r] * ak[0] + R[3 * r + 1] * ak[1]) + R[3 * r + 2] * ak[2]);
     }
     t[r] = scalar_tls(X, range, &tmp);
     for (int k = 0; k < m; ++k) all[k] &= tmp[k];
@@ -408,18 +416,22 @@ extern "C" int pk_teaser_graph(const double* src, const double* dst, const int64
   return PK_OK;
 }
 
-extern "C" int pk_teaser_solve(const double* src, const double* dst, const int64_t* off, int B, int nmax,
-                               const uint64_t* adj, const int32_t* deg, const pk_teaser_params* params, int threads,
-                               double* T, int32_t* clique, int32_t* clique_size, int32_t* info) {
+extern "C" int pk_teaser_solve_scaled(const double* src, const double* dst, const int64_t* off, int B, int nmax,
+                                      const uint64_t* adj, const int32_t* deg, const pk_teaser_params* params,
+                                      int threads, const double* scale, double* T, int32_t* clique,
+                                      int32_t* clique_size, int32_t* info) {
   PK_REQUIRE(B >= 0 && nmax >= 0 && params);
   if (B == 0) return PK_OK;
   PK_REQUIRE(src && dst && off && adj && deg && T && clique && clique_size && info);
   const int W = (nmax + 63) / 64;
   for (int b = 0; b < B; ++b) PK_REQUIRE(off[b + 1] - off[b] >= 0 && off[b + 1] - off[b] <= nmax);
+  if (scale)
+    for (int b = 0; b < B; ++b) PK_REQUIRE(std::isfinite(scale[b]) && scale[b] > 0.0);
   auto work = [&](int b) {
     const int64_t o = off[b];
     solve_one(src + 3 * o, dst + 3 * o, (int)(off[b + 1] - o), adj + (int64_t)b * nmax * W, W,
-              deg + (int64_t)b * nmax, *params, T + 16 * b, clique + (int64_t)b * nmax, clique_size + b, info + 4 * b);
+              deg + (int64_t)b * nmax, *params, scale ? scale[b] : 1.0, T + 16 * b, clique + (int64_t)b * nmax,
+              clique_size + b, info + 4 * b);
   };
   const int nt = std::max(1, std::min(threads, B));
   if (nt == 1) {
@@ -433,4 +445,11 @@ extern "C" int pk_teaser_solve(const double* src, const double* dst, const int64
     for (auto& th : pool) th.join();
   }
   return PK_OK;
+}
+
+extern "C" int pk_teaser_solve(const double* src, const double* dst, const int64_t* off, int B, int nmax,
+                               const uint64_t* adj, const int32_t* deg, const pk_teaser_params* params, int threads,
+                               double* T, int32_t* clique, int32_t* clique_size, int32_t* info) {
+  return pk_teaser_solve_scaled(src, dst, off, B, nmax, adj, deg, params, threads, nullptr, T, clique, clique_size,
+                                info);
 }

@@ -130,6 +130,10 @@ SIGNATURES = {
     "pk_dpotrs": [_P, _P, _I, _I, _I, _P],
     "pk_tufted_laplacian": [_P, _I64, _P, _I64, _D, _I64, _P, _P, _P, _P, _P, _P],
     "pk_teaser_solve": [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P],  # host pointers
+    "pk_teaser_scale_work_size": [_I, _I],
+    "pk_teaser_scale": [_P, _P, _P, _I, _I, _D, _P, _I64, _P, _P, _P],
+    "pk_teaser_graph_scaled": [_P, _P, _P, _I, _I, _D, _P, _P, _P, _P],
+    "pk_teaser_solve_scaled": [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P],  # host pointers
     "pk_transpose_cf_rows": [_P, _P, _I, _I, _I, _I, _I64, _P, _P],
     "pk_mean_f32": [_P, _I64, _P, _P],
     "pk_copy_rows": [_P, _I64, _P, _I64, _I64, _I64, _P],
@@ -143,7 +147,8 @@ SIGNATURES = {
 RESTYPES = {"pk_cgt_lstsq_work_size": _I64, "pk_linear_wgrad_grouped_work": _I64, "pk_ransac_work_size": _I64,
             "pk_feat_dist_work_size": _I64, "pk_fmap_head_work_len": _I64, "pk_icp_work_size": _I64,
             "pk_rigidity_filter_work_size": _I64, "pk_attention_bwd_work_size": _I64,
-            "pk_normals_work_size": _I64, "pk_icp_plane_work_size": _I64}  # everything else returns an int status
+            "pk_normals_work_size": _I64, "pk_icp_plane_work_size": _I64,
+            "pk_teaser_scale_work_size": _I64}  # everything else returns an int status
 
 _lib: Optional[ctypes.CDLL] = None
 _dev_lib: Optional[ctypes.CDLL] = None

@@ -1512,22 +1512,54 @@ def icp(src: torch.Tensor, src_off: torch.Tensor, tgt: torch.Tensor, tgt_off: to
     return T, stats
 
 
-def teaser_graph(src: torch.Tensor, dst: torch.Tensor, off: torch.Tensor, nmax: int, beta: float):
+# Cap on one pk_teaser_scale workspace: ops.teaser(estimate_scaling=True) votes the crops in chunks
+# whose worst-case workspace stays under it (a single crop above the cap still runs alone).
+TEASER_SCALE_WORK_CAP = 4 << 30
+
+
+def teaser_scale(src: torch.Tensor, dst: torch.Tensor, off: torch.Tensor, nmax: int, beta: float,
+                 work: Optional[torch.Tensor] = None):
+    """pk_teaser_scale: TEASER++'s scale vote over the TIM ratios of all pairs of every crop ->
+    (scale f64 [B], scale_info int32 [B, 2] = (1 voted / 0 no usable pair, consensus size)) on the
+    device. `work`: an optional uint8 workspace of at least pk_teaser_scale_work_size bytes."""
+    B = off.numel() - 1
+    nbytes = int(_lib.lib().pk_teaser_scale_work_size(B, int(nmax)))
+    if nbytes < 0:
+        raise _lib.PoseKernError("pk_teaser_scale: nmax must be in [0, 32768]")
+    if work is None:
+        work = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=src.device)
+    scale = torch.empty((max(B, 1),), dtype=torch.float64, device=src.device)
+    info = torch.empty((max(B, 1), 2), dtype=torch.int32, device=src.device)
+    n2 = B * int(nmax) * int(nmax)
+    call("pk_teaser_scale", ptr(src), ptr(dst), ptr(off), B, int(nmax), float(beta), ptr(work), int(work.numel()),
+         ptr(scale), ptr(info), _lib.stream(src.device), work=("hbm", n2 * 24 * 8))  # 8 radix passes
+    return scale[:B], info[:B]
+
+
+def teaser_graph(src: torch.Tensor, dst: torch.Tensor, off: torch.Tensor, nmax: int, beta: float,
+                 scale: Optional[torch.Tensor] = None):
     """pk_teaser_graph: the pairwise-consistency bitsets of every crop's matched point pairs ->
-    (adj uint64 as int64 [B, nmax, ceil(nmax/64)], deg int32 [B, nmax]) on the device."""
+    (adj uint64 as int64 [B, nmax, ceil(nmax/64)], deg int32 [B, nmax]) on the device. With
+    `scale` (f64 [B] on the device) pk_teaser_graph_scaled: the test at each crop's scale."""
     B = off.numel() - 1
     W = (int(nmax) + 63) // 64
     adj = torch.empty((B, max(int(nmax), 1), max(W, 1)), dtype=torch.int64, device=src.device)
     deg = torch.empty((B, max(int(nmax), 1)), dtype=torch.int32, device=src.device)
-    call("pk_teaser_graph", ptr(src), ptr(dst), ptr(off), B, int(nmax), float(beta), ptr(adj), ptr(deg),
-         _lib.stream(src.device), work=("valu64", B * int(nmax) * int(nmax) * 20))
+    if scale is None:
+        call("pk_teaser_graph", ptr(src), ptr(dst), ptr(off), B, int(nmax), float(beta), ptr(adj), ptr(deg),
+             _lib.stream(src.device), work=("valu64", B * int(nmax) * int(nmax) * 20))
+    else:
+        scale = scale.to(dtype=torch.float64).contiguous()
+        call("pk_teaser_graph_scaled", ptr(src), ptr(dst), ptr(off), B, int(nmax), float(beta), ptr(scale), ptr(adj),
+             ptr(deg), _lib.stream(src.device), work=("valu64", B * int(nmax) * int(nmax) * 24))
     return adj, deg
 
 
 def teaser_solve_host(src: np.ndarray, dst: np.ndarray, off: np.ndarray, nmax: int, adj: np.ndarray, deg: np.ndarray,
-                      params, threads: int = 8):
+                      params, threads: int = 8, scale: Optional[np.ndarray] = None):
     """pk_teaser_solve on host arrays (max clique / GNC-TLS / adaptive voting are native host
-    code): (T f64 [B,4,4], clique int32 [B, nmax], clique_size int32 [B], info int32 [B, 4])."""
+    code): (T f64 [B,4,4], clique int32 [B, nmax], clique_size int32 [B], info int32 [B, 4]).
+    With `scale` (f64 [B]) pk_teaser_solve_scaled: adj / deg are the scaled graph."""
     import ctypes
     B = off.shape[0] - 1
     c = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
@@ -1540,27 +1572,52 @@ def teaser_solve_host(src: np.ndarray, dst: np.ndarray, off: np.ndarray, nmax: i
     clique = np.zeros((B, max(int(nmax), 1)), dtype=np.int32)
     size = np.zeros(B, dtype=np.int32)
     info = np.zeros((B, 4), dtype=np.int32)
-    status = _lib.lib().pk_teaser_solve(c(src), c(dst), c(off), B, int(nmax), c(adj), c(deg), ctypes.byref(params),
-                                        int(threads), c(T), c(clique), c(size), c(info))
+    if scale is None:
+        name = "pk_teaser_solve"
+        status = _lib.lib().pk_teaser_solve(c(src), c(dst), c(off), B, int(nmax), c(adj), c(deg),
+                                            ctypes.byref(params), int(threads), c(T), c(clique), c(size), c(info))
+    else:
+        name = "pk_teaser_solve_scaled"
+        scale = np.ascontiguousarray(scale, dtype=np.float64)
+        if scale.shape != (B,):
+            raise _lib.PoseKernError("pk_teaser_solve_scaled: scale must be [B]")
+        status = _lib.lib().pk_teaser_solve_scaled(c(src), c(dst), c(off), B, int(nmax), c(adj), c(deg),
+                                                   ctypes.byref(params), int(threads), c(scale), c(T), c(clique),
+                                                   c(size), c(info))
     if status != 0:
-        raise _lib.PoseKernError(f"pk_teaser_solve failed: {_lib._ERRORS.get(status, status)}")
+        raise _lib.PoseKernError(f"{name} failed: {_lib._ERRORS.get(status, status)}")
     return T, clique, size, info
 
 
 def teaser(src: torch.Tensor, dst: torch.Tensor, off: torch.Tensor, nmax: Optional[int] = None,
            noise_bound: float = 0.05, cbar2: float = 1.0, rotation_gnc_factor: float = 1.4,
            rotation_max_iterations: int = 100, rotation_cost_threshold: float = 1e-12,
-           kcore_heuristic_threshold: float = 0.5, max_clique_nodes: int = 2_000_000, threads: int = 8):
+           kcore_heuristic_threshold: float = 0.5, max_clique_nodes: int = 2_000_000, threads: int = 8,
+           estimate_scaling: bool = False):
     """Batched TEASER++ (pk_teaser_graph on the device, one download of the bitsets, then
-    pk_teaser_solve on host threads). src / dst f64 [T,3] matched pairs packed by off [B+1]."""
+    pk_teaser_solve on host threads). src / dst f64 [T,3] matched pairs packed by off [B+1].
+    estimate_scaling: pk_teaser_scale votes each crop's scale first (in chunks of crops under
+    TEASER_SCALE_WORK_CAP), the graph and the host solve run at that scale, and the result is
+    (T, clique, size, info, scale f64 [B]); T stays the rigid [R | t]."""
     B = off.numel() - 1
     if nmax is None:
         nmax = int((off[1:] - off[:-1]).max()) if B else 0
     p = _lib.TeaserParams(noise_bound, cbar2, rotation_gnc_factor, rotation_cost_threshold, kcore_heuristic_threshold,
                           int(rotation_max_iterations), 0, int(max_clique_nodes))
-    adj, deg = teaser_graph(src, dst, off, nmax, 2.0 * noise_bound * math.sqrt(cbar2))
-    return teaser_solve_host(src.cpu().numpy(), dst.cpu().numpy(), off.cpu().numpy(), nmax,
-                             adj.cpu().numpy(), deg.cpu().numpy(), p, threads)
+    beta = 2.0 * noise_bound * math.sqrt(cbar2)
+    if not estimate_scaling:
+        adj, deg = teaser_graph(src, dst, off, nmax, beta)
+        return teaser_solve_host(src.cpu().numpy(), dst.cpu().numpy(), off.cpu().numpy(), nmax,
+                                 adj.cpu().numpy(), deg.cpu().numpy(), p, threads)
+    per_crop = max(int(_lib.lib().pk_teaser_scale_work_size(1, int(nmax))), 1)
+    step = min(max(1, TEASER_SCALE_WORK_CAP // per_crop), 65535)  # 65535: the entry point's bound on B
+    scales = [teaser_scale(src, dst, off[b0:min(b0 + step, B) + 1].contiguous(), nmax, beta)[0]
+              for b0 in range(0, B, step)]
+    scale = torch.cat(scales) if scales else torch.empty((0,), dtype=torch.float64, device=src.device)
+    adj, deg = teaser_graph(src, dst, off, nmax, beta, scale=scale)
+    scale_h = scale.cpu().numpy()
+    return teaser_solve_host(src.cpu().numpy(), dst.cpu().numpy(), off.cpu().numpy(), nmax, adj.cpu().numpy(),
+                             deg.cpu().numpy(), p, threads, scale=scale_h) + (scale_h,)
 
 
 def knn(pts: torch.Tensor, off: torch.Tensor, nmax: int, k: int, omit_self: bool = True):

@@ -686,6 +686,34 @@ int pk_teaser_solve(const double* src, const double* dst, const int64_t* off, in
                     const int32_t* deg, const pk_teaser_params* params, int threads, double* T, int32_t* clique,
                     int32_t* clique_size, int32_t* info);
 
+/* (f2) TEASER++ scale estimation (estimate_scaling = true, TEASER's TLSScaleSolver): adaptive voting
+ * over the translation-invariant measurements of all pairs (i < j, row-major): X = |dst_j - dst_i| /
+ * |src_j - src_i|, alpha = beta / |src_j - src_i|, beta = 2 noise sqrt(cbar2); the 2 K interval
+ * endpoints X -+ alpha are ordered (stable radix sort on the device) and swept; the scale is the
+ * weighted mean (weights 1 / alpha^2) of the consensus set at the first minimum of the TLS cost.
+ * Build-defined deviation: a pair with |src_j - src_i| == 0 or a non-finite X takes no part in the
+ * vote and is never an edge of the scaled graph (upstream would produce inf / NaN).
+ *   pk_teaser_scale_work_size  bytes of `work` for B crops of at most nmax pairs (the worst case:
+ *     about 26.3 B per endpoint, B nmax (nmax - 1) endpoints); -1 when nmax > 32768.
+ *   pk_teaser_scale (device): src / dst / off as pk_teaser_graph (a crop longer than nmax is cut to
+ *     nmax); scale f64 [B], scale_info int32 [B][2] = (status: 1 voted / 0 no usable pair — then
+ *     scale = 1 —, consensus size at the optimum). Bitwise reproducible, independent of the prior
+ *     contents of `work` and of the other crops of the batch. nmax <= 32768, B <= 65535.
+ *   pk_teaser_graph_scaled (device): pk_teaser_graph with the pair test |X - scale[b]| <= alpha
+ *     (scale f64 [B] on the device); unusable pairs are no edges.
+ *   pk_teaser_solve_scaled (HOST pointers only): pk_teaser_solve on the scaled graph with the
+ *     crop's scale s (scale f64 [B] on the host, each finite and > 0; NULL = all 1, which is
+ *     pk_teaser_solve bit for bit): the crop-side chain TIMs times 1 / s, GNC-TLS noise bound
+ *     2 noise / s, translation voted over dst - s R src. T stays the rigid [R | t]. */
+int64_t pk_teaser_scale_work_size(int B, int nmax);
+int pk_teaser_scale(const double* src, const double* dst, const int64_t* off, int B, int nmax, double beta,
+                    void* work, int64_t work_bytes, double* scale, int32_t* scale_info, void* stream);
+int pk_teaser_graph_scaled(const double* src, const double* dst, const int64_t* off, int B, int nmax, double beta,
+                           const double* scale, uint64_t* adj, int32_t* deg, void* stream);
+int pk_teaser_solve_scaled(const double* src, const double* dst, const int64_t* off, int B, int nmax,
+                           const uint64_t* adj, const int32_t* deg, const pk_teaser_params* params, int threads,
+                           const double* scale, double* T, int32_t* clique, int32_t* clique_size, int32_t* info);
+
 /* (f1) Spectral operators on the device (dataset/object.py:214, 246 -> upstream diffusion-net
  * geometry.compute_operators: robust_laplacian.point_cloud_laplacian for crops, potpourri3d
  * cotan_laplacian + vertex areas for the CAD mesh, scipy eigsh(L + eps I, 64, M, sigma = eps)).
