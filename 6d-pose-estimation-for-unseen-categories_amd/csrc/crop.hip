@@ -276,14 +276,42 @@ constexpr int kKnn = 20;
 constexpr int kSorThreads = 256;
 constexpr int kSorTile = 1024;
 
+// One step of bubbling v into the sorted list: b = min(b, v), v = max(b, v). fmin / fmax compile
+// to v_min_f64 / v_max_f64 plus a canonicalising v_max_f64 x, x, x on every list entry that
+// reaches them through a branch; the values here are squared distances or +inf, never NaN (same
+// reason as vmin_f32 in fps.hip). The list entry is updated in place, so a guarded insertion
+// needs no copies where the branch joins.
+__device__ __forceinline__ void topk_exchange(double& b, double& v) {
+  double hi;
+  asm("v_max_f64 %0, %1, %2\n\tv_min_f64 %1, %1, %2" : "=&v"(hi), "+v"(b) : "v"(v));
+  v = hi;
+}
+
 __device__ __forceinline__ void topk_insert(double (&best)[kKnn], double v) {
 #pragma unroll
-  for (int k = 0; k < kKnn; ++k) {  // bubble v into the sorted list
+  for (int k = 0; k < kKnn; ++k) topk_exchange(best[k], v);
+}
+
+// item number t of a list built from empty (+inf) by t earlier insertions: entries t.. are
+// still +inf, so t exchanges and one move do (20 exchanges from the 21st item on)
+template <int t>
+__device__ __forceinline__ void topk_insert_nth(double (&best)[kKnn], double v) {
+  constexpr int kEx = t < kKnn ? t : kKnn;
+#pragma unroll
+  for (int k = 0; k < kEx; ++k) topk_exchange(best[k], v);
+  if constexpr (t < kKnn) best[t] = v;
+}
+
+#ifdef PK_DEVBUILD
+__device__ __forceinline__ void topk_insert_r6(double (&best)[kKnn], double v) {
+#pragma unroll
+  for (int k = 0; k < kKnn; ++k) {
     const double lo = fmin(best[k], v), hi = fmax(best[k], v);
     best[k] = lo;
     v = hi;
   }
 }
+#endif
 
 __device__ __forceinline__ double sqdist(double ax, double ay, double az, const double* b) {
   const double dx = ax - b[0], dy = ay - b[1], dz = az - b[2];
@@ -346,10 +374,213 @@ __device__ __forceinline__ int sor_gather(const int32_t* __restrict__ row, int u
 }
 
 
+// Row g of a query's 5x5 window: the five coordinate loads are issued together,
+// a pixel without a point contributes +inf (which leaves the list as it is), and item t of the
+// fixed sequence costs min(t, 20) exchanges.
+template <int g>
+__device__ __forceinline__ void sor_window_row(double (&best)[kKnn], const int (&j)[25],
+                                               const double* __restrict__ p, double q0, double q1, double q2) {
+  double c[5][3];
+#pragma unroll
+  for (int e = 0; e < 5; ++e) {
+    const double* pj = p + 3 * (j[5 * g + e] >= 0 ? j[5 * g + e] : 0);
+    c[e][0] = pj[0];
+    c[e][1] = pj[1];
+    c[e][2] = pj[2];
+  }
+  double s[5];
+#pragma unroll
+  for (int e = 0; e < 5; ++e) s[e] = j[5 * g + e] >= 0 ? sqdist(q0, q1, q2, c[e]) : __builtin_huge_val();
+  topk_insert_nth<5 * g + 0>(best, s[0]);
+  topk_insert_nth<5 * g + 1>(best, s[1]);
+  topk_insert_nth<5 * g + 2>(best, s[2]);
+  topk_insert_nth<5 * g + 3>(best, s[3]);
+  topk_insert_nth<5 * g + 4>(best, s[4]);
+}
+
+// pass 2a's pixel box of a query at pixel (u, v) with bound T (see the kernel's comment);
+// false: no usable box (Z_q <= r, a box of 64 px or more, or more than kSorMaxBox pixels)
+__device__ __forceinline__ bool sor_box(const double* __restrict__ Kb, int H, int W, int u, int v, double q0,
+                                        double q1, double q2, double T, int& u0, int& u1, int& v0, int& v1) {
+  const double fx = Kb[0], cx = Kb[2], fy = Kb[4], cy = Kb[5];
+  const double r = sqrt(T) * (1.0 + 1e-9) + 1e-300;
+  if (!(fx > 0.0 && fy > 0.0 && q2 > r)) return false;
+  // a candidate c within r of q: |X_q/Z_q - X_c/Z_c| <= (r/Z_q) sqrt(1 + t_c^2) (Cauchy-
+  // Schwarz on (X_q - X_c) + t_c (Z_c - Z_q)), with |t_c| <= the image bound tx and
+  // |t_c| <= (|t_q| + rho) / (1 - rho), rho = r / Z_q (SOR camera box)
+  const double rho = r / q2;
+  const double tx = fmin(fmax(fabs(cx), fabs((double)(W - 1) - cx)) / fx, (fabs(q0 / q2) + rho) / (1.0 - rho));
+  const double ty = fmin(fmax(fabs(cy), fabs((double)(H - 1) - cy)) / fy, (fabs(q1 / q2) + rho) / (1.0 - rho));
+  const double bu = fx * rho * sqrt(1.0 + tx * tx), bv = fy * rho * sqrt(1.0 + ty * ty);
+  if (!(bu < 64.0 && bv < 64.0)) return false;
+  const int ru = (int)ceil(bu * (1.0 + 1e-9)) + 1, rv = (int)ceil(bv * (1.0 + 1e-9)) + 1;
+  if ((2 * ru + 1) * (2 * rv + 1) > kSorMaxBox) return false;
+  v0 = max(v - rv, 0);
+  v1 = min(v + rv, H - 1);
+  u0 = max(u - ru, 0);
+  u1 = min(u + ru, W - 1);
+  return true;
+}
+
+// pass 2a: best keeps the (2 Rw + 1)^2 window's kk smallest (all <= T, real points), and the
+// box scan adds the box pixels outside that window: the kk smallest of window + box are exact.
+// With T = +inf and the next window as the box it adds that window's ring to the list. Returns
+// the number of points in the scanned pixels.
+__device__ __forceinline__ int sor_box_scan(const int32_t* __restrict__ im, int W, const double* __restrict__ p,
+                                            double q0, double q1, double q2, int u, int v, int Rw, int u0, int u1,
+                                            int v0, int v1, double T, double (&best)[kKnn]) {
+  int found = 0;
+  for (int vv = v0; vv <= v1; ++vv) {
+    const int32_t* row = im + vv * W;
+    const bool in_w = vv >= v - Rw && vv <= v + Rw;  // this row's window pixels are in best
+    for (int seg = 0; seg < 2; ++seg) {
+      const int a = in_w ? (seg == 0 ? u0 : max(u0, u + Rw + 1)) : (seg == 0 ? u0 : 1);
+      const int c = in_w ? (seg == 0 ? min(u1, u - Rw - 1) : u1) : (seg == 0 ? u1 : 0);
+      for (int uu = a; uu <= c; uu += kSorBatch) {
+        double s[kSorBatch];
+        const int m = sor_gather(row, uu, c, p, q0, q1, q2, s);
+#pragma unroll
+        for (int t = 0; t < kSorBatch; ++t)
+          if (((m >> t) & 1) && s[t] <= T && s[t] < best[kKnn - 1]) topk_insert(best, s[t]);
+        found += __builtin_popcount(m);
+      }
+    }
+  }
+  return found;
+}
+
+__device__ __forceinline__ double sor_mean(const double (&best)[kKnn], int kk) {
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < kKnn; ++k)
+    if (k < kk) acc = acc + sqrt_rn(best[k]);
+  return kk > 0 ? acc / (double)kk : -1.0;
+}
+
 // grid (tiles x B): workgroup = (crop, 256-query tile), crops interleaved; a persistent grid
 // (fewer workgroups looping over the items) measured slower with no gain in overlap.
-
+//
+// Every thread first loads the 25 index-map entries of its query's 5x5 window together and
+// builds the list from those pixels as one unrolled sequence. With fewer than kk points there
+// (a query on the mask border) the ring of the 9x9, then of the 17x17 window is added to the
+// list with guarded insertions. Splitting the border queries off into waves of their own after a barrier
+// was measured slower: every workgroup is resident at once, so the kernel
+// takes as long as its longest chain of dependent gathers, and that chain is a border query's.
 __global__ __launch_bounds__(kSorThreads, PK_SOR_MINW) void sor_knn_kernel(const double* __restrict__ xyz,
+                                                                 const int64_t* __restrict__ off, int knn,
+                                                                 const int32_t* __restrict__ pix,
+                                                                 const int32_t* __restrict__ idxmap, int H, int W,
+                                                                 const double* __restrict__ Kmat, int tiles, int B,
+                                                                 double* __restrict__ avg, int prio) {
+  pk::set_wave_prio(prio);
+  __shared__ float4 tile[kSorTile];
+  const int item = blockIdx.x;
+  const int b = item % B, bx = item / B;
+  const int64_t base = off[b];
+  const int n = (int)(off[b + 1] - base);
+  const int i = bx * kSorThreads + threadIdx.x;
+  if (bx * kSorThreads >= n) return;  // workgroup-uniform
+  const bool act = i < n;
+  const double* p = xyz + base * 3;
+  const double ox = p[0], oy = p[1], oz = p[2];
+  const double kInf = __builtin_huge_val();
+  double q0 = 0.0, q1 = 0.0, q2 = 0.0;
+  if (act) {
+    q0 = p[3 * i];
+    q1 = p[3 * i + 1];
+    q2 = p[3 * i + 2];
+  }
+  const int kk = knn < n ? knn : n;
+  double best[kKnn];
+#pragma unroll
+  for (int k = 0; k < kKnn; ++k) best[k] = kInf;
+  double T = kInf;
+  bool done = false;
+  if (act && pix != nullptr && idxmap != nullptr) {
+    const int pp = pix[base + i];
+    const int v = pp / W, u = pp % W;
+    const int32_t* im = idxmap + (int64_t)b * H * W;
+    int found = 0;
+    {
+      int j[25];
+      int cnt = 0;
+#pragma unroll
+      for (int t = 0; t < 25; ++t) {  // all index loads together (clamped: the query's own pixel)
+        const int vv = v + t / 5 - 2, uu = u + t % 5 - 2;
+        const bool inb = vv >= 0 && vv < H && uu >= 0 && uu < W;
+        const int32_t x = im[inb ? vv * W + uu : pp];
+        j[t] = inb ? x : -1;
+        cnt += j[t] >= 0 ? 1 : 0;
+      }
+      sor_window_row<0>(best, j, p, q0, q1, q2);
+      sor_window_row<1>(best, j, p, q0, q1, q2);
+      sor_window_row<2>(best, j, p, q0, q1, q2);
+      sor_window_row<3>(best, j, p, q0, q1, q2);
+      sor_window_row<4>(best, j, p, q0, q1, q2);
+      found = cnt;
+    }
+    int Rw = 2;
+    while (found < kk && Rw > 0) {  // near the mask border: the ring of the 9x9, then of the 17x17 window
+      const int R = 2 * Rw;
+      if (R > 8) {
+        Rw = -1;
+      } else {
+        found += sor_box_scan(im, W, p, q0, q1, q2, u, v, Rw, max(u - R, 0), min(u + R, W - 1), max(v - R, 0),
+                              min(v + R, H - 1), kInf, best);
+        Rw = R;
+      }
+    }
+    if (Rw >= 0) {
+      // T = the kk-th smallest of >= kk real points bounds the true kk-th neighbour distance
+#pragma unroll
+      for (int k = 0; k < kKnn; ++k)
+        if (k == kk - 1) T = best[k];  // static register index (no scratch)
+      int u0 = 0, u1 = -1, v0 = 0, v1 = -1;
+      if (Kmat != nullptr && sor_box(Kmat + 9 * b, H, W, u, v, q0, q1, q2, T, u0, u1, v0, v1)) {
+        sor_box_scan(im, W, p, q0, q1, q2, u, v, Rw, u0, u1, v0, v1, T, best);
+        done = true;
+      }
+    }
+    if (!done) {
+#pragma unroll
+      for (int k = 0; k < kKnn; ++k) best[k] = kInf;
+    }
+  }
+  if (__syncthreads_or(act && !done)) {
+    const float qx = (float)(q0 - ox), qy = (float)(q1 - oy), qz = (float)(q2 - oz);
+    const float qa = fmaxf(fabsf(qx), fmaxf(fabsf(qy), fabsf(qz)));
+    const float Tf = T == kInf ? __builtin_huge_valf() : (float)T;
+    for (int t0 = 0; t0 < n; t0 += kSorTile) {
+      const int tn = min(kSorTile, n - t0);
+      __syncthreads();
+      for (int e = threadIdx.x; e < tn; e += kSorThreads) {
+        const double* c = p + 3 * (t0 + e);
+        const float cx = (float)(c[0] - ox), cy = (float)(c[1] - oy), cz = (float)(c[2] - oz);
+        tile[e] = make_float4(cx, cy, cz, fmaxf(fabsf(cx), fmaxf(fabsf(cy), fabsf(cz))));
+      }
+      __syncthreads();
+      if (act && !done) {
+        for (int e = 0; e < tn; ++e) {
+          const float4 c = tile[e];
+          const float dx = qx - c.x, dy = qy - c.y, dz = qz - c.z;
+          const float d32 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+          const float sa = qa + c.w;
+          const float lim = fmaf(1.9073486e-6f, fmaf(sa, sa, Tf), Tf);  // T + 2^-19 (T + S^2)
+          if (d32 <= lim) {
+            const double s = sqdist(q0, q1, q2, p + 3 * (t0 + e));
+            if (s <= T && s < best[kKnn - 1]) topk_insert(best, s);
+          }
+        }
+      }
+    }
+  }
+  if (act) avg[base + i] = sor_mean(best, kk);
+}
+
+#ifdef PK_DEVBUILD
+// Development A/B (PK_SOR_OLD=1): the round-6 kernel, every query handled by its own thread.
+
+__global__ __launch_bounds__(kSorThreads, PK_SOR_MINW) void sor_knn_kernel_r6(const double* __restrict__ xyz,
                                                                  const int64_t* __restrict__ off, int knn,
                                                                  const int32_t* __restrict__ pix,
                                                                  const int32_t* __restrict__ idxmap, int H, int W,
@@ -396,7 +627,7 @@ __global__ __launch_bounds__(kSorThreads, PK_SOR_MINW) void sor_knn_kernel(const
           const int m = sor_gather(row, uu, u1, p, q0, q1, q2, s);
 #pragma unroll
           for (int t = 0; t < kSorBatch; ++t)
-            if ((m >> t) & 1) topk_insert(best, s[t]);
+            if ((m >> t) & 1) topk_insert_r6(best, s[t]);
           found += __builtin_popcount(m);
         }
       }
@@ -450,7 +681,7 @@ __global__ __launch_bounds__(kSorThreads, PK_SOR_MINW) void sor_knn_kernel(const
             const int m = sor_gather(row, uu, c, p, q0, q1, q2, s);
 #pragma unroll
             for (int t = 0; t < kSorBatch; ++t)
-              if (((m >> t) & 1) && s[t] <= T && s[t] < best[kKnn - 1]) topk_insert(best, s[t]);
+              if (((m >> t) & 1) && s[t] <= T && s[t] < best[kKnn - 1]) topk_insert_r6(best, s[t]);
           }
         }
       }
@@ -482,7 +713,7 @@ __global__ __launch_bounds__(kSorThreads, PK_SOR_MINW) void sor_knn_kernel(const
           const float lim = fmaf(1.9073486e-6f, fmaf(sa, sa, Tf), Tf);  // T + 2^-19 (T + S^2)
           if (d32 <= lim) {
             const double s = sqdist(q0, q1, q2, p + 3 * (t0 + e));
-            if (s <= T && s < best[kKnn - 1]) topk_insert(best, s);
+            if (s <= T && s < best[kKnn - 1]) topk_insert_r6(best, s);
           }
         }
       }
@@ -497,6 +728,7 @@ __global__ __launch_bounds__(kSorThreads, PK_SOR_MINW) void sor_knn_kernel(const
   }
   }
 }
+#endif  // PK_DEVBUILD
 
 // One block per crop: cloud mean over avg > 0, then the Bessel std, accumulated in point
 // order exactly like std::accumulate / std::inner_product: s = s + t_k, k = 0 .. n-1, IEEE
@@ -938,6 +1170,19 @@ extern "C" int pk_sor(const double* xyz, const int64_t* off, int B, int nmax, in
   if (nmax > 0 && !pk::diag_skip("sorknn")) {
     const int tiles = (nmax + kSorThreads - 1) / kSorThreads;
     for (int rep = 0; rep < (pk::diag_twice("sorknn") ? 2 : 1); ++rep) {
+#ifdef PK_DEVBUILD
+      static const bool r6 = [] {  // development knob PK_SOR_OLD=1: the round-6 kernel
+        const char* e = std::getenv("PK_SOR_OLD");
+        return e != nullptr && std::atoi(e) != 0;
+      }();
+      if (r6) {
+        hipLaunchKernelGGL(sor_knn_kernel_r6, dim3((unsigned)((int64_t)tiles * B)), dim3(kSorThreads), 0, s, xyz,
+                           off, knn, pix, idxmap, H, W, pix != nullptr ? K : nullptr, tiles, B, avg,
+                           pk::side_prio());
+        PK_CHECK_LAUNCH();
+        continue;
+      }
+#endif
       hipLaunchKernelGGL(sor_knn_kernel, dim3((unsigned)((int64_t)tiles * B)),
                          dim3(kSorThreads), 0, s, xyz, off, knn, pix, idxmap, H, W,
                          pix != nullptr ? K : nullptr, tiles, B, avg, pk::side_prio());
