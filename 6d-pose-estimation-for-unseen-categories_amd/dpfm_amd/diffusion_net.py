@@ -11,6 +11,8 @@ per direction (ops.spectral_diffusion); the per-point MLPs are GEMMs.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 
@@ -20,6 +22,16 @@ from .layers import Linear
 # The whole configured DiffusionNet as one autograd node (_EncoderFn); False runs the per-module
 # path (the parity tests compare the two)
 FUSED_ENCODER = True
+
+# _EncoderFn runs each block's MLP as one launch per direction (ops.mlp3_fwd / ops.mlp3_bwd,
+# bit-identical to the three per-layer launches); False (PK_BLOCK_MLP_CHAIN=0 at import) runs the
+# per-layer launches — the A/B partner and the tests' reference; "fwd" / "bwd" chain one direction
+# only (the measurements of each direction alone)
+BLOCK_MLP_CHAIN = {"0": False, "fwd": "fwd", "bwd": "bwd"}.get(os.environ.get("PK_BLOCK_MLP_CHAIN", "1"), True)
+
+
+def _chain(direction: str) -> bool:
+    return BLOCK_MLP_CHAIN is True or BLOCK_MLP_CHAIN == direction
 
 
 class LearnedTimeDiffusion(nn.Module):
@@ -55,21 +67,28 @@ class MiniMLP(nn.Sequential):
 
 class _BlockMLPFn(torch.autograd.Function):
     """mlp(cat[x_in, x_diffuse]) + x_in for the configured MiniMLP (128 -> 64 -> 64 -> 64, ReLU
-    between): forward in one fused launch (ops.mlp3_fwd); backward through the per-layer
-    input-gradient kernels, the ReLU masks on the saved h1 / h2, and the weight gradients
-    recorded for the grouped launch (layers.GroupedWgrad) or computed per layer."""
+    between): one launch per direction (ops.mlp3_fwd / ops.mlp3_bwd: the activations stay in the
+    wave between the layers, the ReLU masks on the saved h1 / h2 and the residual are epilogues),
+    and the weight gradients recorded for the grouped launch (layers.GroupedWgrad) or computed
+    per layer."""
 
     @staticmethod
     def forward(ctx, x_in, x_diff, w1, b1, w2, b2, w3, b3):
-        cat, h1, h2, y = ops.mlp3_fwd(x_in, x_diff, w1, b1, w2, b2, w3, b3)
-        ctx.save_for_backward(cat, h1, h2, w1, w2, w3)
+        x_in, x_diff = x_in.contiguous(), x_diff.contiguous()
+        R = x_in.numel() // 64
+        w1, w2, w3 = w1.contiguous(), w2.contiguous(), w3.contiguous()
+        h1 = torch.empty_like(x_in)
+        h2 = torch.empty_like(x_in)
+        y = torch.empty_like(x_in)
+        ops.mlp3_fwd(x_in, x_diff, w1, b1, w2, b2, w3, b3, R, y, h1=h1, h2=h2)
+        ctx.save_for_backward(x_in, x_diff, h1, h2, w1, w2, w3)
         ctx.params = (w1, b1, w2, b2, w3, b3)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         from . import layers
-        cat, h1, h2, w1, w2, w3 = ctx.saved_tensors
+        x_in, x_diff, h1, h2, w1, w2, w3 = ctx.saved_tensors
         P = ctx.params
         dy = dy.contiguous()
         grads = [None] * 6
@@ -78,17 +97,14 @@ class _BlockMLPFn(torch.autograd.Function):
             if layers._side_owns(P[2 * k], P[2 * k + 1]):
                 layers._SIDE.launch(x, d, P[2 * k], P[2 * k + 1], channels_first=False)
             else:
-                grads[2 * k], grads[2 * k + 1] = ops.linear_wgrad(x, d, channels_first=False, want_bias=True)
+                dw, grads[2 * k + 1] = ops.linear_wgrad(x, d, channels_first=False, want_bias=True)
+                grads[2 * k] = dw.view(P[2 * k].shape)
 
+        d2, d1, dx_in, dx_diff = (torch.empty_like(dy) for _ in range(4))
+        ops.mlp3_bwd(dy, h2, h1, w3, w2, w1, dy.numel() // 64, d2, d1, dx_in, dx_diff)
         wgrad(h2, dy, 2)
-        d2 = torch.ops.aten.threshold_backward(ops.linear_fwd(dy, w3, None, channels_first=False, transw=True), h2, 0.0)
         wgrad(h1, d2, 1)
-        d1 = torch.ops.aten.threshold_backward(ops.linear_fwd(d2, w2, None, channels_first=False, transw=True), h1, 0.0)
-        wgrad(cat, d1, 0)
-        dcat = ops.linear_fwd(d1, w1, None, channels_first=False, transw=True)
-        C = dy.shape[-1]
-        dx_in = dcat[..., :C] + dy  # the residual
-        dx_diff = dcat[..., C:].contiguous()
+        wgrad(torch.cat((x_in, x_diff), dim=-1), d1, 0)  # (the module path: not the training step's)
         return (dx_in, dx_diff, *grads)
 
 
@@ -102,9 +118,8 @@ class DiffusionNetBlock(nn.Module):
         self.diffusion = LearnedTimeDiffusion(C_width, method=diffusion_method)
         self.mlp = MiniMLP([2 * C_width] + list(mlp_hidden_dims) + [C_width], dropout=dropout)
 
-    # The fused block forward (pk_mlp3_fwd) is opt-in: on MI355X it measured no faster than the
-    # per-layer kernels it replaces (46 us vs 20 + 12 + 12 us of layer launches plus the concat
-    # and the residual add: one 8-wave block per CU, 103 KB of LDS), DESIGN.md §3
+    # The module path's own block node (_BlockMLPFn on pk_mlp3_fwd / pk_mlp3_bwd) is opt-in: the
+    # configured network runs as _EncoderFn, which uses the same kernels in place (BLOCK_MLP_CHAIN)
     fused_mlp = False
 
     def _fusable(self, x_in) -> bool:
@@ -147,7 +162,7 @@ class _EncoderFn(torch.autograd.Function):
     Same arithmetic per layer as the module path (models/dpfm.py:22-30; upstream layers.py)."""
 
     @staticmethod
-    def forward(ctx, fcat, mass, evals, evecs, nblock, *params):
+    def forward(ctx, fcat, mass, evals, evecs, nblock, save, *params):
         R = fcat.shape[0] * fcat.shape[1]
         B, N = fcat.shape[0], fcat.shape[1]
         dev = fcat.device
@@ -162,13 +177,20 @@ class _EncoderFn(torch.autograd.Function):
         for i, (t, w1, b1, w2, b2, w3, b3) in enumerate(blocks):
             cat = cats[i]
             raws.append(ops.spectral_raw(cat, 128, mass, evals, evecs, t, True, 0, cat[..., 64:], 128))
+            nxt = cats[i + 1] if i + 1 < nblock else Y
+            ldy = 128 if i + 1 < nblock else 0
+            if _chain("fwd") and not save:  # save: grad mode at the call; off, h1 / h2 are not stored
+                ops.mlp3_fwd(cat, cat[..., 64:], w1, b1, w2, b2, w3, b3, R, nxt, ld_in=128, ld_diff=128, ldy=ldy)
+                continue
             h1 = torch.empty((B, N, 64), dtype=torch.float32, device=dev)
             h2 = torch.empty_like(h1)
-            ops.linear_ex(cat, w1, b1, 0, R, 0, 128, 64, y=h1, relu=True)
-            ops.linear_ex(h1, w2, b2, 0, R, 0, 64, 64, y=h2, relu=True)
-            nxt = cats[i + 1] if i + 1 < nblock else Y
-            ops.linear_ex(h2, w3, b3, 0, R, 0, 64, 64, y=nxt, ldy=128 if i + 1 < nblock else 0, add=cat, lda=128,
-                          add_cols=64)
+            if _chain("fwd"):
+                ops.mlp3_fwd(cat, cat[..., 64:], w1, b1, w2, b2, w3, b3, R, nxt, ld_in=128, ld_diff=128, ldy=ldy,
+                             h1=h1, h2=h2)
+            else:
+                ops.linear_ex(cat, w1, b1, 0, R, 0, 128, 64, y=h1, relu=True)
+                ops.linear_ex(h1, w2, b2, 0, R, 0, 64, 64, y=h2, relu=True)
+                ops.linear_ex(h2, w3, b3, 0, R, 0, 64, 64, y=nxt, ldy=ldy, add=cat, lda=128, add_cols=64)
             h1s.append(h1)
             h2s.append(h2)
         feat = torch.empty((B, N, Cout), dtype=torch.float32, device=dev)
@@ -204,15 +226,21 @@ class _EncoderFn(torch.autograd.Function):
             k = 2 + 7 * i
             grads[k + 5], grads[k + 6] = _wgrad(h2s[i], dy, w3, b3)
             d2 = torch.empty_like(dy)
-            ops.linear_ex(dy, w3, None, 0, R, 0, 64, 64, y=d2, transw=True, mask=h2s[i])
-            grads[k + 3], grads[k + 4] = _wgrad(h1s[i], d2, w2, b2)
             d1 = torch.empty_like(dy)
-            ops.linear_ex(d2, w2, None, 0, R, 0, 64, 64, y=d1, transw=True, mask=h1s[i])
-            grads[k + 1], grads[k + 2] = _wgrad(cats[i], d1, w1, b1)
             dX = torch.empty_like(dy)
             dD = torch.empty_like(dy)
-            # dcat = d1 W1: columns 0..63 (+ the residual's dy) -> dX, 64..127 -> dD
-            ops.linear_ex(d1, w1, None, 0, R, 0, 64, 128, y=dX, transw=True, y2=dD, split=64, add=dy, add_cols=64)
+            chain = _chain("bwd")
+            if chain:  # the three input-gradient layers below as one launch
+                ops.mlp3_bwd(dy, h2s[i], h1s[i], w3, w2, w1, R, d2, d1, dX, dD)
+            else:
+                ops.linear_ex(dy, w3, None, 0, R, 0, 64, 64, y=d2, transw=True, mask=h2s[i])
+            grads[k + 3], grads[k + 4] = _wgrad(h1s[i], d2, w2, b2)
+            if not chain:
+                ops.linear_ex(d2, w2, None, 0, R, 0, 64, 64, y=d1, transw=True, mask=h1s[i])
+            grads[k + 1], grads[k + 2] = _wgrad(cats[i], d1, w1, b1)
+            if not chain:
+                # dcat = d1 W1: columns 0..63 (+ the residual's dy) -> dX, 64..127 -> dD
+                ops.linear_ex(d1, w1, None, 0, R, 0, 64, 128, y=dX, transw=True, y2=dD, split=64, add=dy, add_cols=64)
             # dL/dt straight into t's persistent .grad when the grouped weight gradient owns it (no
             # autograd accumulation launch)
             from . import layers
@@ -226,7 +254,7 @@ class _EncoderFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:  # the features are data in DPFM; kept for API completeness
             dfcat = torch.empty_like(fcat)
             ops.linear_ex(dy, w0, None, 0, R, 0, 64, fcat.shape[-1], y=dfcat, transw=True)
-        return (dfcat, None, None, None, None, *grads)
+        return (dfcat, None, None, None, None, None, *grads)
 
 
 class DiffusionNet(nn.Module):
@@ -276,7 +304,7 @@ class DiffusionNet(nn.Module):
         ps = self._fused_params(x_in) if evecs is not None and evecs.shape[-1] == 64 else None
         if ps is not None and FUSED_ENCODER:
             x = _EncoderFn.apply(x_in.contiguous(), mass.contiguous(), evals.contiguous(), evecs.contiguous(),
-                                 len(self.blocks), *ps)
+                                 len(self.blocks), torch.is_grad_enabled(), *ps)
             return x[0] if appended else x
         x = self.first_lin(x_in)
         for b in self.blocks:

@@ -986,22 +986,31 @@ def overlap_head(fx: torch.Tensor, fy: torch.Tensor, w0, b0, w1, b1):
     return _OverlapHeadFn.apply(fx, fy, w0, b0, w1, b1)
 
 
-def mlp3_fwd(x_in: torch.Tensor, x_diff: torch.Tensor, w1, b1, w2, b2, w3, b3):
-    """pk_mlp3_fwd: (cat, h1, h2, y) of the DiffusionNet block MLP with its residual."""
-    x_in, x_diff = x_in.contiguous(), x_diff.contiguous()
-    C = x_in.shape[-1]
-    R = x_in.numel() // C
-    lead = x_in.shape[:-1]
-    dev = x_in.device
-    cat = torch.empty(lead + (2 * C,), dtype=torch.float32, device=dev)
-    h1 = torch.empty(lead + (C,), dtype=torch.float32, device=dev)
-    h2 = torch.empty_like(h1)
-    y = torch.empty_like(h1)
-    byts = 4 * R * (2 * C + 2 * C + 3 * C + C)  # reads x_in, x_diff (+x_in again), writes cat, h1, h2, y
-    call("pk_mlp3_fwd", ptr(x_in), ptr(x_diff), ptr(w1.contiguous()), ptr(b1), ptr(w2.contiguous()), ptr(b2),
-         ptr(w3.contiguous()), ptr(b3), int(R), int(C), ptr(cat), ptr(h1), ptr(h2), ptr(y), _lib.stream(dev),
-         work=("hbm", byts, 2 * R * C * (2 * C + C + C)))
-    return cat, h1, h2, y
+_MLP3_WEIGHT_BYTES = 4 * (64 * 128 + 2 * 64 * 64)
+
+
+def mlp3_fwd(x_in: torch.Tensor, x_diff: torch.Tensor, w1, b1, w2, b2, w3, b3, R: int, y: torch.Tensor,
+             ld_in: int = 0, ld_diff: int = 0, ldy: int = 0, h1: Optional[torch.Tensor] = None,
+             h2: Optional[torch.Tensor] = None, max_blocks: int = 0) -> None:
+    """pk_mlp3_fwd: the DiffusionNet block MLP with its residual in one launch. x_in, x_diff, y
+    are the first elements of R rows of 64 at row strides ld_in / ld_diff / ldy (0: contiguous;
+    the halves of one [R, 128] buffer: cat[..., :64], cat[..., 64:] with 128); h1 / h2 contiguous
+    [R, 64] outputs for the backward, or both None (not stored)."""
+    C = 64
+    call("pk_mlp3_fwd", ctypes_ptr(x_in), int(ld_in), ctypes_ptr(x_diff), int(ld_diff), ptr(w1), ptr(b1), ptr(w2),
+         ptr(b2), ptr(w3), ptr(b3), int(R), C, ptr(h1), ptr(h2), ctypes_ptr(y), int(ldy), int(max_blocks),
+         _lib.stream(y.device),
+         work=("hbm", 4 * R * (2 * C + (3 if h1 is not None else 1) * C) + _MLP3_WEIGHT_BYTES, 2 * R * C * 4 * C))
+
+
+def mlp3_bwd(dy: torch.Tensor, h2: torch.Tensor, h1: torch.Tensor, w3, w2, w1, R: int, d2: torch.Tensor,
+             d1: torch.Tensor, dx: torch.Tensor, dd: torch.Tensor, max_blocks: int = 0) -> None:
+    """pk_mlp3_bwd: the block MLP's three input-gradient layers with the ReLU masks and the
+    residual's dy in one launch; every operand contiguous [R, 64] (weights as stored)."""
+    C = 64
+    call("pk_mlp3_bwd", ptr(dy), ptr(h2), ptr(h1), ptr(w3), ptr(w2), ptr(w1), int(R), C, ptr(d2), ptr(d1), ptr(dx),
+         ptr(dd), int(max_blocks), _lib.stream(dy.device),
+         work=("hbm", 4 * R * (3 * C + 2 * C + 2 * C) + _MLP3_WEIGHT_BYTES, 2 * R * C * 4 * C))
 
 
 def linear_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], channels_first: bool,

@@ -339,14 +339,24 @@ typedef struct pk_overlap_head_args {
 int pk_overlap_head_fwd(const pk_overlap_head_args* a, void* stream);
 int pk_overlap_head_bwd(const pk_overlap_head_args* a, void* stream);
 
-/* H7 DiffusionNet block MLP forward, fused (upstream DiffusionNetBlock.forward at
+/* H7 DiffusionNet block MLP, one launch per direction (upstream DiffusionNetBlock.forward at
  * models/dpfm.py:22-30: mlp(cat[x_in, x_diffuse]) + x_in, MiniMLP 128 -> 64 -> ReLU -> 64 ->
- * ReLU -> 64). x_in / x_diff f32 [R, C], C = 64; W1 [64, 128], W2 / W3 [64, 64], biases
- * [64]; writes cat [R, 128], h1 / h2 [R, 64] (post-ReLU, kept for the backward) and
- * y [R, 64] = h2 W3^T + b3 + x_in. */
-int pk_mlp3_fwd(const float* x_in, const float* x_diff, const float* w1, const float* b1, const float* w2,
-                const float* b2, const float* w3, const float* b3, int64_t R, int C, float* cat, float* h1, float* h2,
-                float* y, void* stream);
+ * ReLU -> 64), C = 64; W1 [64, 128], W2 / W3 [64, 64], biases [64]. The activations stay in the
+ * wave between the layers; every output is bit-identical to the three pk_linear_ex launches.
+ * Forward: x_in / x_diff f32 rows of 64 at element row strides ld_in / ld_diff (0: 64; the two
+ *   halves of one [R, 128] buffer: cat, cat + 64 with 128); writes h1 = relu(cat W1^T + b1),
+ *   h2 = relu(h1 W2^T + b2) (contiguous [R, 64], kept for the backward; both NULL: not stored)
+ *   and y = (h2 W3^T + b3) + x_in at row stride ldy (0: 64).
+ * Backward: dy, h2, h1 contiguous [R, 64]; writes d2 = (h2 <= 0 ? 0 : dy W3),
+ *   d1 = (h1 <= 0 ? 0 : d2 W2) (the weight gradients' operands), dx = (d1 W1)[:, :64] + dy and
+ *   dd = (d1 W1)[:, 64:], all contiguous [R, 64].
+ * Pointers 16-B aligned, strides % 4 == 0. max_blocks caps the grid (0: 256 blocks of 4 waves; a
+ * wave walks its 16-row tiles grid-stride). */
+int pk_mlp3_fwd(const float* x_in, int64_t ld_in, const float* x_diff, int64_t ld_diff, const float* w1,
+                const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, int64_t R, int C,
+                float* h1, float* h2, float* y, int64_t ldy, int max_blocks, void* stream);
+int pk_mlp3_bwd(const float* dy, const float* h2, const float* h1, const float* w3, const float* w2, const float* w1,
+                int64_t R, int C, float* d2, float* d1, float* dx, float* dd, int max_blocks, void* stream);
 
 /* H9 fmap head around the solve (modeling/dpfm.py:154-176, models/dpfm.py:66-72), K = 30,
  * C = 32: W = evecs[:, :K] * mass (f32 products); A = W_x^T F_x, Bm = W_y^T F_y [B,K,C];

@@ -16,7 +16,7 @@ shapes = [  # (lead, Cin, Cout, cf, transw)  lead = rows (cl) or (B, N) (cf)
     (65536, 32, 64, False, True), ((32, 1024), 32, 32, True, False), ((32, 1024), 64, 64, True, False),
     ((32, 1024), 64, 32, True, False), ((32, 1024), 32, 64, True, True), ((32, 1024), 32, 1, True, False), ((32, 1024), 1, 32, True, True), (65536, 32, 1, False, False),
 ]
-for lead, ci, co, cf, tw in shapes:
+for lead, ci, co, cf, tw in ([] if "--block-only" in sys.argv else shapes):  # --block-only: the block launches below
     if cf:
         B, N = lead
         x = torch.randn(B, ci, N, device=dev)
@@ -66,6 +66,31 @@ cases = [
     ("bwd 64->64 T mask", lambda: ops.linear_ex(h, w3, None, 0, R, 0, 64, 64, y=o64, transw=True, mask=m), 192),
     ("bwd 64->128 T split+add", lambda: ops.linear_ex(h, w1, None, 0, R, 0, 64, 128, y=o64, transw=True, y2=o64b,
                                                       split=64, add=m, add_cols=64), 256),
+]
+# the block MLP as one chain per direction (pk_mlp3_fwd / pk_mlp3_bwd) beside the three layers each replaces
+o64c, o64d = torch.empty(R, 64, device=dev), torch.empty(R, 64, device=dev)
+
+
+def fwd_layers():
+    ops.linear_ex(cat, w1, b, 0, R, 0, 128, 64, y=o64, relu=True)
+    ops.linear_ex(o64, w2, b, 0, R, 0, 64, 64, y=o64b, relu=True)
+    ops.linear_ex(o64b, w3, b, 0, R, 0, 64, 64, y=o128, ldy=128, add=cat, lda=128, add_cols=64)
+
+
+def bwd_layers():
+    ops.linear_ex(h, w3, None, 0, R, 0, 64, 64, y=o64, transw=True, mask=m)
+    ops.linear_ex(o64, w2, None, 0, R, 0, 64, 64, y=o64b, transw=True, mask=m)
+    ops.linear_ex(o64b, w1, None, 0, R, 0, 64, 128, y=o64c, transw=True, y2=o64d, split=64, add=h, add_cols=64)
+
+
+cases += [
+    ("block fwd, 3 layers", fwd_layers, 128 + 3 * 64),
+    ("block fwd, chain", lambda: ops.mlp3_fwd(cat, cat[:, 64:], w1, b, w2, b, w3, b, R, o128, ld_in=128, ld_diff=128,
+                                              ldy=128, h1=o64, h2=o64b), 128 + 3 * 64),
+    ("block fwd, chain, no h1/h2", lambda: ops.mlp3_fwd(cat, cat[:, 64:], w1, b, w2, b, w3, b, R, o128, ld_in=128,
+                                                        ld_diff=128, ldy=128), 128 + 64),
+    ("block bwd, 3 layers", bwd_layers, 3 * 64 + 2 * 64 + 128),
+    ("block bwd, chain", lambda: ops.mlp3_bwd(h, m, m, w3, w2, w1, R, o64, o64b, o64c, o64d), 3 * 64 + 2 * 64 + 128),
 ]
 for name, f, bpr in cases:
     for _ in range(3):
