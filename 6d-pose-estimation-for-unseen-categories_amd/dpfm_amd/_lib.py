@@ -130,6 +130,12 @@ SIGNATURES = {
     "pk_dpotrf": [_P, _I, _I, _D, _P, _P],
     "pk_dpotrs": [_P, _P, _I, _I, _I, _P],
     "pk_tufted_laplacian": [_P, _I64, _P, _I64, _D, _I64, _P, _P, _P, _P, _P, _P],
+    "pk_grad_build": [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P],
+    "pk_grad_apply": [_P, _I64, _P, _P, _I, _I, _I, _I, _P, _P],
+    "pk_grad_apply_t": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I64, _I, _P],
+    "pk_gradfeat_fwd": [_P, _P, _P, _I64, _I, _P, _I64, _P],
+    "pk_gradfeat_bwd": [_P, _I64, _P, _I64, _P, _P, _P, _I64, _I, _P, _P, _P],
+    "pk_linear192_fwd": [_P, _I64, _P, _P, _I64, _I, _P, _P],
     "pk_teaser_solve": [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P],  # host pointers
     "pk_teaser_scale_work_size": [_I, _I],
     "pk_teaser_scale": [_P, _P, _P, _I, _I, _D, _P, _I64, _P, _P, _P],

@@ -22,6 +22,7 @@ import torch
 # the operator fields the training / eval scripts move to the device (helpers.py:6)
 DEVICE_FIELDS = ("xyz", "faces", "mass", "evals", "evecs", "gradX", "gradY")
 MASKED_FIELDS = ("n",)  # collate(counts=True)'s true lengths: moved with the operator fields
+GRAD_FIELDS = ("grad",)  # collate(grads=True)'s GradOperator (has its own .to)
 SPARSE_FIELDS = ("L", "gradX", "gradY")
 
 
@@ -35,10 +36,18 @@ def pad_batch(arrays: Sequence[np.ndarray]) -> torch.Tensor:
     return batch
 
 
-def _shape_part(crops: Sequence[dict], counts: bool = False) -> dict:
+def _shape_part(crops: Sequence[dict], counts: bool = False, grads: bool = False) -> dict:
     first = crops[0]
     part = {key: (pad_batch([c[key] for c in crops]) if isinstance(first[key], np.ndarray) else None)
             for key in first}
+    if grads:  # the crops' sparse gradX / gradY as one fixed-width operator (gradient features)
+        from ..geometry import GradOperator
+        if any(c.get("gradX") is None or c.get("gradY") is None for c in crops):
+            raise ValueError('collate(grads=True) needs every crop\'s sparse "gradX" and "gradY"')
+        as_sparse = lambda m: m if m.is_sparse else m.to_sparse()  # noqa: E731
+        part["grad"] = GradOperator.from_coo([as_sparse(torch.as_tensor(c["gradX"])) for c in crops],
+                                             [as_sparse(torch.as_tensor(c["gradY"])) for c in crops],
+                                             dtype=torch.float32, nmax=int(part["xyz"].shape[1]))
     if counts:  # the unpadded lengths, for the masked mode (DPFMNet(masked=True))
         part["n"] = torch.tensor([int(np.asarray(c["xyz"]).shape[0]) for c in crops], dtype=torch.int32)
     return part
@@ -57,12 +66,15 @@ def _obj_part(crops: Sequence[dict]) -> dict:
     return out
 
 
-def collate(data, counts: bool = False):
+def collate(data, counts: bool = False, grads: bool = False):
     """(CAD, PC, Obj) batch of a list of `base_object_dataset` items (helpers.py:22-50).
     counts=True: each shape dict gains "n", the int32 [B] unpadded point counts the masked mode
-    reads (the reference keeps no such record: it does not mask its padding)."""
+    reads (the reference keeps no such record: it does not mask its padding).
+    grads=True: each shape dict gains "grad", the crops' sparse gradX / gradY as one
+    geometry.GradOperator (f32, padded like the other fields) for DPFMNet(with_gradient_features=
+    True); gradX / gradY themselves stay None, as in the reference."""
     cads, pcs, objs = zip(*[(item[0], item[1], item[2]) for item in data])
-    return _shape_part(cads, counts), _shape_part(pcs, counts), _obj_part(objs)
+    return _shape_part(cads, counts, grads), _shape_part(pcs, counts, grads), _obj_part(objs)
 
 
 def collate_noprocess(data):
@@ -80,7 +92,7 @@ def shape_to_device(batch: dict, device) -> dict:
     for key in list(batch):
         entry = batch[key]
         if "shape" in key:
-            for field in DEVICE_FIELDS + MASKED_FIELDS:
+            for field in DEVICE_FIELDS + MASKED_FIELDS + GRAD_FIELDS:
                 if entry.get(field) is not None:
                     entry[field] = entry[field].to(device)
         elif isinstance(entry, list):

@@ -8,6 +8,12 @@ names as weights/weights.pt (`first_lin`, `block_{i}.diffusion.diffusion_time`,
 
 The diffusion step (to_basis -> exp(-lambda t) -> from_basis) runs in one fused HIP kernel
 per direction (ops.spectral_diffusion); the per-point MLPs are GEMMs.
+
+with_gradient_features=True (upstream's default, off in the reference configuration) adds
+SpatialGradientFeatures to every block: the spatial gradient of the diffused features through the
+fixed-width gradient operator (geometry.GradOperator; ops.grad_apply), a learned complex rotation
+and the tanh of the per-channel inner product (ops.gradfeat_fwd), concatenated as a third 64-wide
+input of the block MLP. Such a network runs the module path (not _EncoderFn).
 """
 from __future__ import annotations
 
@@ -108,15 +114,80 @@ class _BlockMLPFn(torch.autograd.Function):
         return (dx_in, dx_diff, *grads)
 
 
+class SpatialGradientFeatures(nn.Module):
+    """Upstream layers.SpatialGradientFeatures: from the spatial gradient (vX, vY) of each channel,
+    B = A v as a complex product (with_gradient_rotations: B_re = A_re vX - A_im vY, B_im = A_re vY +
+    A_im vX; else B_re = A vX, B_im = A vY; bias-free [C, C] layers under upstream's names) and the
+    feature tanh(vX . B_re + vY . B_im). forward takes upstream's [..., C, 2] (real, imaginary)
+    vectors or the kernels' packed [..., 2C] = [vX | vY]; one launch per direction (C = 64)."""
+
+    def __init__(self, C_inout, with_gradient_rotations=True):
+        super().__init__()
+        self.C_inout = C_inout
+        self.with_gradient_rotations = with_gradient_rotations
+        if with_gradient_rotations:
+            self.A_re = nn.Linear(C_inout, C_inout, bias=False)
+            self.A_im = nn.Linear(C_inout, C_inout, bias=False)
+        else:
+            self.A = nn.Linear(C_inout, C_inout, bias=False)
+
+    def weights(self):
+        """(A_re, A_im) or (A, None): the kernels' weight operands."""
+        if self.with_gradient_rotations:
+            return self.A_re.weight, self.A_im.weight
+        return self.A.weight, None
+
+    def forward(self, vectors):
+        C = self.C_inout
+        if vectors.dim() >= 3 and vectors.shape[-1] == 2 and vectors.shape[-2] == C:
+            vectors = torch.cat((vectors[..., 0], vectors[..., 1]), dim=-1)
+        if C != 64 or vectors.shape[-1] != 128 or vectors.dtype != torch.float32:
+            raise ops._lib.PoseKernError("gradient features kernels are built for f32, C_width = 64")
+        return ops._GradFeatFn.apply(vectors, *self.weights())
+
+
+class _Linear192Fn(torch.autograd.Function):
+    """relu(cat W^T + b) for the 192-input first MLP layer of a block with gradient features
+    (pk_linear192_fwd: pk_linear_ex stops at 128 inputs). Backward: the ReLU mask, the input
+    gradient as two transposed products written side by side into one [R, 192] buffer (columns
+    0..127 and 128..191), the weight gradient as two pk_linear_wgrad column blocks."""
+
+    @staticmethod
+    def forward(ctx, cat, weight, bias):
+        cat = cat.contiguous()
+        w = weight.contiguous()
+        R = cat.numel() // 192
+        y = torch.empty(cat.shape[:-1] + (64,), dtype=torch.float32, device=cat.device)
+        ops.linear192_fwd(cat, 192, w, bias, R, True, y)
+        ctx.save_for_backward(cat, w, y)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        cat, w, y = ctx.saved_tensors
+        R = cat.numel() // 192
+        dy = torch.ops.aten.threshold_backward(dy.contiguous(), y, 0.0)
+        dcat = torch.empty_like(cat)
+        ops.linear_ex(dy, w[:, :128].contiguous(), None, 0, R, 0, 64, 128, y=dcat, ldy=192, transw=True)
+        ops.linear_ex(dy, w[:, 128:].contiguous(), None, 0, R, 0, 64, 64, y=dcat[..., 128:], ldy=192, transw=True)
+        dw0, db = ops.linear_wgrad(cat[..., :128], dy, channels_first=False, want_bias=ctx.has_bias)
+        dw1, _ = ops.linear_wgrad(cat[..., 128:], dy, channels_first=False, want_bias=False)
+        return dcat, torch.cat((dw0, dw1), dim=1), db
+
+
 class DiffusionNetBlock(nn.Module):
     def __init__(self, C_width, mlp_hidden_dims, dropout=False, diffusion_method="spectral",
                  with_gradient_features=False, with_gradient_rotations=True):
         super().__init__()
-        if with_gradient_features:
-            raise ValueError("gradient features are off in the reference config (models/dpfm.py:28)")
         self.C_width = C_width
+        self.with_gradient_features = with_gradient_features
         self.diffusion = LearnedTimeDiffusion(C_width, method=diffusion_method)
-        self.mlp = MiniMLP([2 * C_width] + list(mlp_hidden_dims) + [C_width], dropout=dropout)
+        self.MLP_C = 2 * C_width
+        if with_gradient_features:
+            self.gradient_features = SpatialGradientFeatures(C_width, with_gradient_rotations=with_gradient_rotations)
+            self.MLP_C += C_width
+        self.mlp = MiniMLP([self.MLP_C] + list(mlp_hidden_dims) + [C_width], dropout=dropout)
 
     # The module path's own block node (_BlockMLPFn on pk_mlp3_fwd / pk_mlp3_bwd) is opt-in: the
     # configured network runs as _EncoderFn, which uses the same kernels in place (BLOCK_MLP_CHAIN)
@@ -129,8 +200,28 @@ class DiffusionNetBlock(nn.Module):
                 and all(l.bias is not None for l in lins)
                 and [tuple(l.weight.shape) for l in lins] == [(64, 128), (64, 64), (64, 64)])
 
+    def _forward_grad(self, x_in, x_diffuse, grad):
+        """mlp(cat[x_in, x_diffuse, g]) + x_in, g = the gradient features of x_diffuse on the
+        GradOperator `grad`: the concatenation is one [B, N, 192] buffer the gradient kernels read
+        and write in place (ops._GradCatFn), the 192-input layer its own launch (_Linear192Fn)."""
+        mods = list(self.mlp)
+        if (grad is None or self.C_width != 64 or not isinstance(mods[0], Linear) or not mods[0].relu_out
+                or tuple(mods[0].weight.shape) != (64, 192) or x_in.dtype != torch.float32):
+            if grad is None:
+                raise ValueError("a DiffusionNet with gradient features needs gradX (a geometry.GradOperator, or "
+                                 "per-crop sparse gradX / gradY)")
+            raise ops._lib.PoseKernError("gradient features kernels are built for f32, C_width = 64 and a ReLU MLP")
+        cat = ops._GradCatFn.apply(x_in.contiguous(), x_diffuse.contiguous(), grad.idx, grad.val, grad.tptr,
+                                   grad.tsrc, *self.gradient_features.weights())
+        h = _Linear192Fn.apply(cat, mods[0].weight, mods[0].bias)
+        for m in mods[1:]:
+            h = m(h)
+        return h + x_in
+
     def forward(self, x_in, mass, L, evals, evecs, gradX, gradY):
         x_diffuse = self.diffusion(x_in, L, mass, evals, evecs)
+        if self.with_gradient_features:
+            return self._forward_grad(x_in, x_diffuse, gradX)
         if self._fusable(x_in):  # the configured block: one fused forward launch
             l0, l1, l2 = [m for m in self.mlp if isinstance(m, Linear)]
             return _BlockMLPFn.apply(x_in, x_diffuse, l0.weight, l0.bias, l1.weight, l1.bias, l2.weight, l2.bias)
@@ -280,6 +371,8 @@ class DiffusionNet(nn.Module):
 
     def _fused_params(self, x_in):
         """The parameter list of _EncoderFn when this is the configured network, else None."""
+        if any(b.with_gradient_features for b in self.blocks):
+            return None  # gradient features run the module path
         if not (x_in.is_cuda and x_in.dtype == torch.float32 and self.C_width == 64 and self.last_activation is None
                 and self.first_lin.in_features <= 4 and self.last_lin.out_features in (16, 32, 64)):
             return None
@@ -297,10 +390,28 @@ class DiffusionNet(nn.Module):
             return None
         return ps
 
+    @staticmethod
+    def _grad_operator(gradX, gradY, x_in):
+        from .geometry import GradOperator
+        if not isinstance(gradX, GradOperator):
+            if torch.is_tensor(gradX):
+                gradX, gradY = [gradX], [gradY]
+            gradX = GradOperator.from_coo(list(gradX), list(gradY), nmax=x_in.shape[1])
+        if gradX.val.dtype != torch.float32 or gradX.val.device != x_in.device:
+            gradX = gradX.to(device=x_in.device, dtype=torch.float32)
+        if gradX.idx.shape[1] != x_in.shape[1]:
+            raise ValueError(f"gradX covers {gradX.idx.shape[1]} points per crop, x_in has {x_in.shape[1]}")
+        return gradX
+
     def forward(self, x_in, mass, L=None, evals=None, evecs=None, gradX=None, gradY=None, edges=None, faces=None):
+        """gradX: a geometry.GradOperator (val f32, on x_in's device), or — upstream-style batches —
+        gradX / gradY as per-crop lists of sparse [n, n] tensors (one sparse tensor each for a single
+        unbatched shape), converted with GradOperator.from_coo. Read only with gradient features."""
         appended = x_in.dim() == 2
         if appended:
             x_in, mass, evals, evecs = x_in[None], mass[None], evals[None], evecs[None]
+        if gradX is not None and any(b.with_gradient_features for b in self.blocks):
+            gradX = self._grad_operator(gradX, gradY, x_in)
         ps = self._fused_params(x_in) if evecs is not None and evecs.shape[-1] == 64 else None
         if ps is not None and FUSED_ENCODER:
             x = _EncoderFn.apply(x_in.contiguous(), mass.contiguous(), evals.contiguous(), evecs.contiguous(),

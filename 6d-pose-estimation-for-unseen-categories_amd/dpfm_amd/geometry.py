@@ -19,8 +19,9 @@ operators: N <= ~5000 per shape (200 MB for the CAD), well inside HBM.
 
 Returns what compute_operators returns that the model reads (mass, L, evals, evecs) plus the
 tangent frames (build_tangent_frames from the PCA normals of the crop's 30-neighbourhoods, or the
-mesh's area-weighted vertex normals); gradX / gradY feed only gradient features, which this model
-configuration does not use (models/dpfm.py:22-30, with_gradient_features=False), and are None.
+mesh's area-weighted vertex normals) and the gradient operators gradX / gradY (build_grad on the
+30-neighbour table of a cloud or the edge neighbours of a mesh: GradOperator, pk_grad_build), which
+feed DiffusionNet's gradient features (off in the reference configuration, models/dpfm.py:22-30).
 Parity unpinned."""
 from __future__ import annotations
 
@@ -34,6 +35,100 @@ from . import ops
 
 
 @dataclass
+class GradOperator:
+    """The gradient operators gradX / gradY of a batch (upstream build_grad: a complex [n, n] sparse
+    matrix per shape, gradX its real and gradY its imaginary part) in the fixed-width layout the
+    gradient-feature kernels read (ops.grad_apply / grad_apply_t):
+      idx  int32 [B, nmax, W]     crop-local column of each slot; slot 0 = the point itself,
+                                  -1 = empty; rows past a crop's count are empty
+      val  [B, nmax, W, 2]        (gradX, gradY) entry of the slot (0 in empty slots)
+      tptr int32 [B, nmax + 1], tsrc int32 [B, nmax W]: the inverted index of the transposed apply:
+                                  destination j's contributions e = row W + slot are
+                                  tsrc[b, tptr[b, j] : tptr[b, j + 1]], ascending.
+    get_operators builds it in fp64 (ops.grad_build); the layer reads it as f32 (.float())."""
+    idx: torch.Tensor
+    val: torch.Tensor
+    tptr: torch.Tensor
+    tsrc: torch.Tensor
+    counts: tuple
+
+    @staticmethod
+    def build(idx: torch.Tensor, val: torch.Tensor, counts: Sequence[int]) -> "GradOperator":
+        tptr, tsrc = GradOperator.inverted_index(idx)
+        return GradOperator(idx.contiguous(), val.contiguous(), tptr, tsrc, tuple(int(c) for c in counts))
+
+    @staticmethod
+    def inverted_index(idx: torch.Tensor):
+        """(tptr, tsrc) of idx [B, N, W]: a stable sort of the flat positions row W + slot by their
+        destination, so each destination's list is ascending; empty slots sort past every list."""
+        B, N, W = idx.shape
+        flat = idx.reshape(B, N * W).long()
+        key = torch.where(flat >= 0, flat, torch.full_like(flat, N))
+        tsrc = torch.sort(key, dim=1, stable=True).indices.to(torch.int32)
+        cnt = torch.zeros((B, N + 1), dtype=torch.int64, device=idx.device)
+        cnt.scatter_add_(1, key, torch.ones_like(key))
+        tptr = torch.zeros((B, N + 1), dtype=torch.int64, device=idx.device)
+        tptr[:, 1:] = cnt[:, :N].cumsum(1)
+        return tptr.to(torch.int32).contiguous(), tsrc.contiguous()
+
+    def to(self, device=None, dtype=None) -> "GradOperator":
+        mv = lambda t: t.to(device=device) if device is not None else t  # noqa: E731
+        val = mv(self.val)
+        if dtype is not None:
+            val = val.to(dtype)
+        return GradOperator(mv(self.idx), val.contiguous(), mv(self.tptr), mv(self.tsrc), self.counts)
+
+    def float(self) -> "GradOperator":
+        return self.to(dtype=torch.float32)
+
+    def coo(self, b: int):
+        """Upstream's (gradX, gradY) of crop b: sparse COO [n, n], coalesced, in val's dtype."""
+        n = self.counts[b]
+        idx, val = self.idx[b, :n], self.val[b, :n]
+        rows = torch.arange(n, device=idx.device)[:, None].expand_as(idx)
+        keep = idx >= 0
+        ij = torch.stack((rows[keep], idx[keep].long()))
+        v = val[keep]
+        return tuple(torch.sparse_coo_tensor(ij, v[:, c], (n, n)).coalesce() for c in range(2))
+
+    @staticmethod
+    def from_coo(gradX: Sequence[torch.Tensor], gradY: Sequence[torch.Tensor], device=None,
+                 dtype=None, nmax: Optional[int] = None) -> "GradOperator":
+        """From per-crop sparse [n, n] gradX / gradY (e.g. an upstream operator cache); W = the
+        longest row (its off-diagonal entries + the diagonal slot), nmax = the largest n unless
+        given (the padded length of the batch the operator goes with)."""
+        rows = []
+        for gx, gy in zip(gradX, gradY):
+            n = int(gx.shape[0])
+            gx, gy = gx.detach().cpu().coalesce(), gy.detach().cpu().coalesce()
+            # the union of the two patterns (upstream's are equal: one complex matrix), values [nnz, 2]
+            ix, iy = gx.indices().numpy(), gy.indices().numpy()
+            kx, ky = ix[0] * n + ix[1], iy[0] * n + iy[1]
+            keys, inv = np.unique(np.concatenate((kx, ky)), return_inverse=True)
+            v = np.zeros((keys.shape[0], 2), gx.values().numpy().dtype)
+            v[inv[:kx.shape[0]], 0] = gx.values().numpy()
+            v[inv[kx.shape[0]:], 1] = gy.values().numpy()
+            rows.append((n, keys // n, keys % n, v))
+        nmax = max([n for n, _, _, _ in rows] + [int(nmax or 0)])
+        W = 1 + max([int(np.bincount(r[r != c], minlength=1).max()) if (r != c).any() else 0 for _, r, c, _ in rows])
+        W = max(W, 2)
+        vdt = rows[0][3].dtype
+        idx = np.full((len(rows), nmax, W), -1, np.int32)
+        val = np.zeros((len(rows), nmax, W, 2), vdt)
+        for b, (n, r, c, v) in enumerate(rows):
+            idx[b, :n, 0] = np.arange(n)
+            d = r == c
+            val[b, r[d], 0] = v[d]
+            ro, co, vo = r[~d], c[~d], v[~d]  # row-major, ascending column (coalesced)
+            deg = np.bincount(ro, minlength=n)
+            pos = np.arange(ro.shape[0]) - np.repeat(np.cumsum(deg) - deg, deg)
+            idx[b, ro, 1 + pos] = co
+            val[b, ro, 1 + pos] = vo
+        op = GradOperator.build(torch.from_numpy(idx), torch.from_numpy(val), [n for n, _, _, _ in rows])
+        return op.to(device=device, dtype=dtype)
+
+
+@dataclass
 class SpectralOperators:
     mass: torch.Tensor     # f64 [B, nmax]
     L: torch.Tensor        # f64 [B, nmax, nmax] dense cotan Laplacian
@@ -43,8 +138,51 @@ class SpectralOperators:
     iterations: int
     residual: torch.Tensor  # f64 [B] max eigen-residual / spectral bound over the k pairs
     frames: Optional[torch.Tensor] = None  # f64 [T, 3, 3] (basisX, basisY, normal) per point
-    gradX = None
-    gradY = None
+    grad: Optional[GradOperator] = None    # the gradient operators (fp64), fixed-width
+
+    @property
+    def gradX(self):
+        """Upstream's gradX per crop (sparse [n, n]), or None without gradient operators."""
+        return None if self.grad is None else [self.grad.coo(b)[0] for b in range(len(self.grad.counts))]
+
+    @property
+    def gradY(self):
+        return None if self.grad is None else [self.grad.coo(b)[1] for b in range(len(self.grad.counts))]
+
+
+def mesh_neighbor_table(faces: Sequence[np.ndarray], counts: Sequence[int]) -> np.ndarray:
+    """Every vertex's edge neighbours from the faces (unique, ascending), as one packed int32
+    [T, Wm] table of crop-local indices padded with -1 (host preprocessing; Wm = the largest degree)."""
+    per = []
+    for f, n in zip(faces, counts):
+        f = np.asarray(f, dtype=np.int64).reshape(-1, 3)
+        e = np.concatenate((f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]))
+        e = np.concatenate((e, e[:, ::-1]))
+        e = np.unique(e[e[:, 0] != e[:, 1]], axis=0)  # sorted by (i, j)
+        per.append((e, np.bincount(e[:, 0], minlength=n)))
+    Wm = max(1, max(int(d.max()) if d.size else 0 for _, d in per))
+    out = []
+    for (e, deg), n in zip(per, counts):
+        t = np.full((n, Wm), -1, np.int32)
+        pos = np.arange(e.shape[0]) - np.repeat(np.cumsum(deg) - deg, deg)
+        t[e[:, 0], pos] = e[:, 1]
+        out.append(t)
+    return np.concatenate(out)
+
+
+def build_grad_operator(pts: torch.Tensor, off: torch.Tensor, counts: Sequence[int], frames: torch.Tensor,
+                        nbr: torch.Tensor) -> GradOperator:
+    """The batch's gradient operators from its packed points, tangent frames and outgoing
+    neighbour table (int32 [T, W - 1], -1 = empty): one pk_grad_build launch + the inverted index.
+    Each row of the table is first put in ascending order, empties last (a kNN table comes sorted
+    by distance): the slots, and with them the order of every sum, are then those of
+    GradOperator.from_coo(coo(b)), so an operator that went through a cache gives the same bits."""
+    nbr = nbr.to(torch.int32)
+    big = torch.iinfo(torch.int32).max
+    nbr = torch.where(nbr < 0, torch.full_like(nbr, big), nbr).sort(dim=1).values
+    nbr = torch.where(nbr == big, torch.full_like(nbr, -1), nbr).contiguous()
+    idx, val = ops.grad_build(pts, off, max(counts), frames, nbr)
+    return GradOperator.build(idx, val, counts)
 
 
 def tangent_frames(normals: torch.Tensor) -> torch.Tensor:
@@ -170,7 +308,8 @@ def get_operators(verts: Sequence[np.ndarray], faces: Optional[Sequence[np.ndarr
                               fmax=int(max(f.shape[0] for f in faces)), scale=1.0, denom_eps=1e-10)
     for b, n in enumerate(counts):  # vertex_areas + eps * mean (compute_operators)
         mass[b, :n] += eps * mass[b, :n].mean()
-    return _spectral(pts, off, counts, L, mass, None, k_eig, eps, faces=faces, **eig_kw)
+    nbr = torch.as_tensor(mesh_neighbor_table(faces, counts), device=dev)
+    return _spectral(pts, off, counts, L, mass, None, k_eig, eps, faces=faces, nbr=nbr, **eig_kw)
 
 
 def point_cloud_operators(pts: torch.Tensor, off: torch.Tensor, counts: Sequence[int], k_eig: int = 64,
@@ -193,7 +332,7 @@ def point_cloud_operators(pts: torch.Tensor, off: torch.Tensor, counts: Sequence
         L, mass = tufted_dense(pts, off, counts, nmax, tri, ntri, mollify_factor)
     else:
         L, mass = ops.cotan_dense(pts, off, nmax, tri=tri, ntri=ntri, scale=1.0 / 3.0, denom_eps=0.0)
-    return _spectral(pts, off, counts, L, mass, normals, k_eig, eps, **eig_kw)
+    return _spectral(pts, off, counts, L, mass, normals, k_eig, eps, nbr=idx, **eig_kw)
 
 
 def tufted_dense(pts, off, counts, nmax, tri, ntri, mollify_factor=1e-5):
@@ -225,8 +364,9 @@ def tufted_dense(pts, off, counts, nmax, tri, ntri, mollify_factor=1e-5):
     return L, mass
 
 
-def _spectral(pts, off, counts, L, mass, normals, k_eig, eps, faces=None, **eig_kw) -> SpectralOperators:
-    """eigsh(L + eps I, k, M = diag(mass), sigma) for the assembled operators, then the frames."""
+def _spectral(pts, off, counts, L, mass, normals, k_eig, eps, faces=None, nbr=None, **eig_kw) -> SpectralOperators:
+    """eigsh(L + eps I, k, M = diag(mass), sigma) for the assembled operators, then the frames and
+    the gradient operators on the neighbour table nbr."""
     dev = L.device
     for b, n in enumerate(counts):
         mass[b, n:] = 1.0
@@ -241,5 +381,7 @@ def _spectral(pts, off, counts, L, mass, normals, k_eig, eps, faces=None, **eig_
         fl = torch.cat([torch.as_tensor(np.asarray(f, dtype=np.int64), device=dev) + int(o)
                         for f, o in zip(faces, off[:-1].cpu().tolist())])
         normals = mesh_vertex_normals(pts, fl)
+    frames = tangent_frames(normals)
+    grad = build_grad_operator(pts, off, counts, frames, nbr) if nbr is not None else None
     return SpectralOperators(mass=mass, L=L, evals=evals.clamp(min=0.0), evecs=evecs, normals=normals,
-                             iterations=iters, residual=res, frames=tangent_frames(normals))
+                             iterations=iters, residual=res, frames=frames, grad=grad)

@@ -10,6 +10,11 @@ ref_feat1, ref_feat2). state_dict keys equal weights/weights.pt.
 from the reference, which lets collate's zero padding into the attention's softmax and the
 InstanceNorm statistics): each shape dict also carries "n", the crops' true point counts, and the
 refiner sees only real points, so a crop's result does not depend on its batch's padding.
+
+`DPFMNet(cfg, with_gradient_features=True)` builds the encoder as upstream DPFM configures it
+(DiffusionNet with gradient features and rotations): each shape dict also carries "grad", the
+shape's geometry.GradOperator (get_operators(...).grad, or collate(grads=True) from per-crop sparse
+gradX / gradY). The default False leaves parameters, keys and results as the reference's.
 """
 from __future__ import annotations
 
@@ -47,12 +52,14 @@ def _cat0(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 class DPFMNet(nn.Module):
     """Compute the functional map matrix representation."""
 
-    def __init__(self, cfg=None, masked: bool = False):
+    def __init__(self, cfg=None, masked: bool = False, with_gradient_features: bool = False):
         super().__init__()
         cfg = cfg or DEFAULT_CFG
         self.masked = bool(masked)  # (no parameter or buffer: state_dict keys are unchanged)
+        self.with_gradient_features = bool(with_gradient_features)
         self.feature_extractor = DiffusionNet(C_in=cfg["fmap"]["C_in"], C_out=cfg["fmap"]["n_feat"], C_width=64,
-                                              N_block=2, dropout=False, with_gradient_features=False,
+                                              N_block=2, dropout=False,
+                                              with_gradient_features=self.with_gradient_features,
                                               with_gradient_rotations=True)
         a = cfg["attention"]
         self.feat_refiner = CrossAttentionRefinementNet(
@@ -75,7 +82,15 @@ class DPFMNet(nn.Module):
             if verts1.dim() != 3:
                 raise ValueError("masked DPFMNet takes batched [B, N, 3] shapes")
             lengths = (s1["n"], s2["n"])
-        if verts1.dim() == 3 and verts1.shape == verts2.shape and evecs1.shape == evecs2.shape:
+        grad1 = grad2 = None
+        if self.with_gradient_features:
+            for key, s in (("shape1", s1), ("shape2", s2)):
+                if s.get("grad") is None:
+                    raise ValueError(f'DPFMNet(with_gradient_features=True) needs the gradient operator batch["{key}"]'
+                                     '["grad"] (a geometry.GradOperator: get_operators(...).grad / collate(grads=True))')
+            grad1, grad2 = s1["grad"], s2["grad"]
+        if (verts1.dim() == 3 and verts1.shape == verts2.shape and evecs1.shape == evecs2.shape
+                and not self.with_gradient_features):  # (the two shapes' operators differ in width)
             # same weights, per-crop operations: one pass over both shapes (2B crops); the
             # input features (v - 110) / 50 of both shapes (models/dpfm.py:53) in one launch
             B = verts1.shape[0]
@@ -90,8 +105,8 @@ class DPFMNet(nn.Module):
         else:
             fused_cat = False
             features1, features2 = (verts1 - 110) / 50, (verts2 - 110) / 50  # models/dpfm.py:53
-            feat1 = self.feature_extractor(features1, mass1, evals=evals1, evecs=evecs1)
-            feat2 = self.feature_extractor(features2, mass2, evals=evals2, evecs=evecs2)
+            feat1 = self.feature_extractor(features1, mass1, evals=evals1, evecs=evecs1, gradX=grad1)
+            feat2 = self.feature_extractor(features2, mass2, evals=evals2, evecs=evecs2, gradX=grad2)
 
         ref_feat1, ref_feat2, overlap_score12, overlap_score21 = self.feat_refiner(
             verts1, verts2, feat1, feat2, batch, features_xy=feat if fused_cat else None, lengths=lengths)

@@ -1800,3 +1800,172 @@ def sample_features(fmap: torch.Tensor, K: torch.Tensor, pts: torch.Tensor, off:
     call("pk_sample_features", ptr(fmap.contiguous()), F_, C, H, W, ptr(K), ptr(pts), ptr(off), int(nmax), ptr(out),
          _lib.stream(fmap.device))
     return out
+
+
+# ------------------------------------------------------------------------------ gradient features
+
+
+def grad_build(pts: torch.Tensor, off: torch.Tensor, nmax: int, frames: torch.Tensor, nbr: torch.Tensor):
+    """pk_grad_build: the fixed-width gradient operator of a packed batch. pts f64 [T, 3], frames f64
+    [T, 3, 3], nbr int32 [T, W - 1] (crop-local outgoing neighbours, -1 = empty) -> (idx int32
+    [B, nmax, W], val f64 [B, nmax, W, 2]); slot 0 is the point itself."""
+    B = off.numel() - 1
+    W = int(nbr.shape[1]) + 1
+    dev = pts.device
+    idx = torch.empty((B, int(nmax), W), dtype=torch.int32, device=dev)
+    val = torch.empty((B, int(nmax), W, 2), dtype=torch.float64, device=dev)
+    call("pk_grad_build", ptr(pts.contiguous()), ptr(off), B, int(nmax), ptr(frames.contiguous()),
+         ptr(nbr.to(torch.int32).contiguous()), W, ptr(idx), ptr(val), _lib.stream(dev))
+    return idx, val
+
+
+def _grad_shapes(idx: torch.Tensor, val: torch.Tensor):
+    if idx.dtype != torch.int32 or val.dtype != torch.float32 or idx.dim() != 3 or val.shape != idx.shape + (2,):
+        raise _lib.PoseKernError("gradient features take idx int32 [B, N, W] and val f32 [B, N, W, 2]")
+    return idx.shape
+
+
+def grad_apply(x: torch.Tensor, ldx: int, idx: torch.Tensor, val: torch.Tensor,
+               v: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pk_grad_apply: v [B, N, 128] = [gradX x | gradY x]. x: the first element of B N rows of 64
+    floats at row stride ldx (a column range of a wider buffer, or a contiguous [B, N, 64])."""
+    B, N, W = _grad_shapes(idx, val)
+    if v is None:
+        v = torch.empty((B, N, 128), dtype=torch.float32, device=idx.device)
+    # algorithmic bytes: x in, v out, the operator (indices + coefficient pairs)
+    call("pk_grad_apply", _dp(x), int(ldx), ptr(idx), ptr(val), B, N, W, 64, ptr(v), _lib.stream(idx.device),
+         work=("hbm", 4 * B * N * (64 + 128 + 3 * W)))
+    return v
+
+
+def grad_apply_t(dv: torch.Tensor, tptr: torch.Tensor, tsrc: torch.Tensor, val: torch.Tensor, dx: torch.Tensor,
+                 lddx: int, accumulate: bool = False) -> None:
+    """pk_grad_apply_t: dx (rows of 64 at stride lddx) = or += gradX^T dv[..., :64] + gradY^T
+    dv[..., 64:] through the inverted index (tptr int32 [B, N + 1], tsrc int32 [B, N W])."""
+    B, N, W = val.shape[:3]
+    if (val.dtype != torch.float32 or tptr.dtype != torch.int32 or tsrc.dtype != torch.int32
+            or tuple(tptr.shape) != (B, N + 1) or tuple(tsrc.shape) != (B, N * W) or tuple(dv.shape) != (B, N, 128)):
+        raise _lib.PoseKernError("grad_apply_t: dv [B, N, 128], tptr int32 [B, N + 1], tsrc int32 [B, N W]")
+    call("pk_grad_apply_t", ptr(dv), ptr(tptr), ptr(tsrc), ptr(val), B, N, W, 64, _dp(dx), int(lddx), int(accumulate),
+         _lib.stream(dv.device), work=("hbm", 4 * B * N * (128 + 64 * (2 if accumulate else 1) + 3 * W)))
+
+
+def gradfeat_fwd(v: torch.Tensor, A_re: torch.Tensor, A_im: Optional[torch.Tensor], R: int, g: torch.Tensor,
+                 ldg: int) -> None:
+    """pk_gradfeat_fwd: g (rows of 64 at stride ldg) = tanh(vX . B_re + vY . B_im) over R rows of
+    v [R, 128] (A_im None: no rotations)."""
+    if tuple(A_re.shape) != (64, 64) or (A_im is not None and tuple(A_im.shape) != (64, 64)):
+        raise _lib.PoseKernError("gradient features kernels are built for C_width = 64")
+    call("pk_gradfeat_fwd", ptr(v), ptr(A_re), ptr(A_im), int(R), 64, _dp(g), int(ldg), _lib.stream(v.device),
+         work=("mfma", 2 * int(R) * 128 * 128))
+
+
+def gradfeat_bwd(dg: torch.Tensor, lddg: int, g: torch.Tensor, ldg: int, v: torch.Tensor, A_re: torch.Tensor,
+                 A_im: Optional[torch.Tensor], R: int):
+    """pk_gradfeat_bwd -> (dv [R, 128], pq [2, R, 64]: P = ds . vX, Q = ds . vY)."""
+    if tuple(A_re.shape) != (64, 64) or (A_im is not None and tuple(A_im.shape) != (64, 64)):
+        raise _lib.PoseKernError("gradient features kernels are built for C_width = 64")
+    dv = torch.empty((int(R), 128), dtype=torch.float32, device=v.device)
+    pq = torch.empty((2, int(R), 64), dtype=torch.float32, device=v.device)
+    call("pk_gradfeat_bwd", _dp(dg), int(lddg), _dp(g), int(ldg), ptr(v), ptr(A_re), ptr(A_im), int(R), 64, ptr(dv),
+         ptr(pq), _lib.stream(v.device), work=("mfma", 4 * int(R) * 128 * 128))
+    return dv, pq
+
+
+def gradfeat_wgrad(v: torch.Tensor, pq: torch.Tensor, rotations: bool):
+    """(dA_re, dA_im or None) from pk_gradfeat_bwd's operands: two pk_linear_wgrad launches on the
+    stacked input v = [vX | vY] (P^T v = [P^T vX | P^T vY], Q^T v likewise), combined as
+    dA_re = P^T vX + Q^T vY, dA_im = Q^T vX - P^T vY (64 x 64 adds)."""
+    R = pq.shape[1]
+    v2 = v.reshape(R, 128)
+    wp, _ = linear_wgrad(v2, pq[0], channels_first=False, want_bias=False)
+    wq, _ = linear_wgrad(v2, pq[1], channels_first=False, want_bias=False)
+    d_re = wp[:, :64] + wq[:, 64:]
+    return d_re, (wq[:, :64] - wp[:, 64:]) if rotations else None
+
+
+def linear192_fwd(x: torch.Tensor, ldx: int, w: torch.Tensor, bias: Optional[torch.Tensor], R: int, relu: bool,
+                  y: torch.Tensor) -> None:
+    """pk_linear192_fwd: y [R, 64] = act(x W^T + b), x rows of 192 floats at stride ldx, W [64, 192]."""
+    if tuple(w.shape) != (64, 192) or not w.is_contiguous():
+        raise _lib.PoseKernError("linear192_fwd: the weight must be contiguous [64, 192]")
+    call("pk_linear192_fwd", _dp(x), int(ldx), ptr(w), ptr(bias), int(R), int(relu), ptr(y), _lib.stream(y.device),
+         work=("hbm", 4 * int(R) * (192 + 64) + 4 * 64 * 192, 2 * int(R) * 192 * 64))
+
+
+class _GradApplyFn(torch.autograd.Function):
+    """v = [gradX x | gradY x] (pk_grad_apply); backward the transposed apply (pk_grad_apply_t)."""
+
+    @staticmethod
+    def forward(ctx, x, idx, val, tptr, tsrc):
+        x = x.contiguous()
+        ctx.save_for_backward(val, tptr, tsrc)
+        return grad_apply(x, 64, idx, val)
+
+    @staticmethod
+    def backward(ctx, dv):
+        val, tptr, tsrc = ctx.saved_tensors
+        dv = dv.contiguous()
+        dx = torch.empty(dv.shape[:2] + (64,), dtype=torch.float32, device=dv.device)
+        grad_apply_t(dv, tptr, tsrc, val, dx, 64)
+        return dx, None, None, None, None
+
+
+class _GradFeatFn(torch.autograd.Function):
+    """g = tanh(vX . B_re + vY . B_im) over rows of v [..., 128] (pk_gradfeat_fwd / pk_gradfeat_bwd;
+    the weight gradients through pk_linear_wgrad). A_im None: without rotations."""
+
+    @staticmethod
+    def forward(ctx, v, A_re, A_im):
+        v = v.contiguous()
+        A_re = A_re.contiguous()
+        A_im = A_im.contiguous() if A_im is not None else None
+        R = v.numel() // 128
+        g = torch.empty(v.shape[:-1] + (64,), dtype=torch.float32, device=v.device)
+        gradfeat_fwd(v, A_re, A_im, R, g, 64)
+        ctx.save_for_backward(v, g, A_re, A_im)
+        return g
+
+    @staticmethod
+    def backward(ctx, dg):
+        v, g, A_re, A_im = ctx.saved_tensors
+        dg = dg.contiguous()
+        R = v.numel() // 128
+        dv, pq = gradfeat_bwd(dg, 64, g, 64, v, A_re, A_im, R)
+        d_re, d_im = gradfeat_wgrad(v, pq, A_im is not None)
+        return dv.view(v.shape), d_re, d_im
+
+
+class _GradCatFn(torch.autograd.Function):
+    """The input of a block MLP with gradient features, cat[x_in, x_diffuse, g] as one [B, N, 192]
+    buffer: x_in and x_diffuse copied into columns 0..127, pk_grad_apply reading x_diffuse there
+    (row stride 192), pk_gradfeat_fwd writing g into columns 128..191. Backward: g's gradient read
+    in place from columns 128..191 of the buffer's gradient, and the transposed apply added
+    (accumulate) into x_diffuse's share, columns 64..127."""
+
+    @staticmethod
+    def forward(ctx, x_in, x_diff, idx, val, tptr, tsrc, A_re, A_im):
+        B, N, W = _grad_shapes(idx, val)
+        if tuple(x_in.shape) != (B, N, 64) or tuple(x_diff.shape) != (B, N, 64):
+            raise _lib.PoseKernError("gradient features: x [B, N, 64] must match the operator's [B, N, W]")
+        A_re = A_re.contiguous()
+        A_im = A_im.contiguous() if A_im is not None else None
+        cat = torch.empty((B, N, 192), dtype=torch.float32, device=x_in.device)
+        cat[..., :64].copy_(x_in)
+        cat[..., 64:128].copy_(x_diff)
+        v = grad_apply(cat[..., 64:], 192, idx, val)
+        gradfeat_fwd(v, A_re, A_im, B * N, cat[..., 128:], 192)
+        ctx.save_for_backward(cat, v, val, tptr, tsrc, A_re, A_im)
+        return cat
+
+    @staticmethod
+    def backward(ctx, dcat):
+        cat, v, val, tptr, tsrc, A_re, A_im = ctx.saved_tensors
+        B, N = cat.shape[:2]
+        dcat = dcat.contiguous()
+        dv, pq = gradfeat_bwd(dcat[..., 128:], 192, cat[..., 128:], 192, v, A_re, A_im, B * N)
+        dx_in = dcat[..., :64].contiguous()
+        dx_diff = dcat[..., 64:128].contiguous()
+        grad_apply_t(dv.view(B, N, 128), tptr, tsrc, val, dx_diff, 64, accumulate=True)
+        d_re, d_im = gradfeat_wgrad(v, pq, A_im is not None)
+        return dx_in, dx_diff, None, None, None, None, d_re, d_im

@@ -771,6 +771,49 @@ int pk_tufted_laplacian(const double* pts, int64_t n, const int32_t* tri, int64_
                         int64_t cap, int32_t* ii, int32_t* jj, double* ww, int64_t* nnz, double* mass,
                         int64_t* nflips);
 
+/* (f1) Gradient operators (upstream diffusion-net geometry.build_grad / build_grad_point_cloud /
+ * edge_tangent_vectors; parity unpinned). Per point i of a packed batch (pts f64 [T,3], off [B+1],
+ * frames f64 [T,3,3] rows (basisX, basisY, normal)) with the outgoing neighbours nbr int32
+ * [T, W-1] (crop-local, -1 = empty; an entry equal to i or outside the crop counts as empty):
+ * a_t = ((p_j - p_i) . basisX_i, (p_j - p_i) . basisY_i), M = sum_t a_t a_t^T + 1e-5 I,
+ * c_t = M^-1 a_t, c_0 = -sum_t c_t, every sum in slot order. Fixed-width rows: idx int32
+ * [B,nmax,W] (slot 0 = i, slot t = nbr slot t-1, -1 = empty; rows past a crop's count all -1),
+ * val f64 [B,nmax,W,2] (gradX, gradY components; 0 in empty slots). One launch; W >= 2. */
+int pk_grad_build(const double* pts, const int64_t* off, int B, int nmax, const double* frames, const int32_t* nbr,
+                  int W, int32_t* idx, double* val, void* stream);
+
+/* DiffusionNet gradient features (upstream layers.py SpatialGradientFeatures) on the fixed-width
+ * operator above, f32, C = 64 channels (PK_ERR_ARG otherwise). Rows are addressed by their first
+ * element and a row stride in floats (a multiple of 4, >= the row's width; 16-byte aligned
+ * pointers), so operands can be column ranges of a wider buffer.
+ *   pk_grad_apply    v[b,i,0:64] = sum_s val[b,i,s,0] x[b,idx[b,i,s],:], v[b,i,64:128] the same
+ *                    with val[..,1]; sums in slot order; empty slots add nothing (padded rows: 0).
+ *                    x rows at stride ldx (crop b at row b N); v contiguous [B,N,128].
+ *   pk_grad_apply_t  the transposed apply through the inverted index: dx[b,j,:] (= or +=, by
+ *                    `accumulate`) sum over e in tsrc[b, tptr[b,j] .. tptr[b,j+1]) of
+ *                    val[b,e,0] dv[b, e / W, 0:64] + val[b,e,1] dv[b, e / W, 64:128], e = row W + slot
+ *                    in list order (no atomics: bitwise reproducible). tptr int32 [B,N+1], tsrc
+ *                    int32 [B,N W]; dv contiguous [B,N,128]; dx rows at stride lddx.
+ *   pk_gradfeat_fwd  g = tanh(vX . B_re + vY . B_im) with B_re = vX A_re^T - vY A_im^T, B_im =
+ *                    vY A_re^T + vX A_im^T (A_im NULL: B_re = vX A^T, B_im = vY A^T with A = A_re)
+ *                    over R rows of v [R,128] on the f32 MFMA; g rows at stride ldg.
+ *   pk_gradfeat_bwd  from dg (stride lddg) and the saved g (stride ldg): dv [R,128] contiguous and
+ *                    P = ds . vX, Q = ds . vY (ds = dg (1 - g^2); pq [2,R,64] contiguous), the
+ *                    operands of the weight gradients dA_re = P^T vX + Q^T vY, dA_im = Q^T vX -
+ *                    P^T vY (pk_linear_wgrad). B is recomputed.
+ *   pk_linear192_fwd y [R,64] = act(x W^T + b) for rows of 192 inputs at stride ldx (the first MLP
+ *                    layer of a block with gradient features; W [64,192], relu 0 / 1). */
+int pk_grad_apply(const float* x, int64_t ldx, const int32_t* idx, const float* val, int B, int N, int W, int C,
+                  float* v, void* stream);
+int pk_grad_apply_t(const float* dv, const int32_t* tptr, const int32_t* tsrc, const float* val, int B, int N, int W,
+                    int C, float* dx, int64_t lddx, int accumulate, void* stream);
+int pk_gradfeat_fwd(const float* v, const float* A_re, const float* A_im, int64_t R, int C, float* g, int64_t ldg,
+                    void* stream);
+int pk_gradfeat_bwd(const float* dg, int64_t lddg, const float* g, int64_t ldg, const float* v, const float* A_re,
+                    const float* A_im, int64_t R, int C, float* dv, float* pq, void* stream);
+int pk_linear192_fwd(const float* x, int64_t ldx, const float* w, const float* bias, int64_t R, int relu, float* y,
+                     void* stream);
+
 /* pk_copy_rows: rows blocks of n floats from src (block stride ld_src floats) to dst (ld_dst):
  * the x half of torch.cat([x, message], dim=1) (modeling/dpfm.py:67) in the fused
  * AttentionalPropagation node's [B, 2C, N] buffer (rows = B, n = C N, ld_dst = 2 C N). */
