@@ -418,6 +418,9 @@ def fmap_head(fx, fy, evecs_x, evecs_y, mass_x, mass_y, evals_x, evals_y, lambda
 
 
 def fmap_solve(AAt: torch.Tensor, BAt: torch.Tensor, D: torch.Tensor, lambda_: float) -> torch.Tensor:
+    """C[b, i, :] = (AAt_b + lambda diag(D_b[i])) ^-1 BAt_b[i, :], f32 [B, 30, 30] each. The forward
+    takes any nonsingular system; the backward requires a symmetric AAt (it solves with M_i where
+    the general gradient needs M_i^T)."""
     if AAt.shape[-1] != 30:
         raise _lib.PoseKernError("fmap solve kernel is built for n_fmap = 30")
     return _FmapSolve.apply(AAt, BAt, D, lambda_)

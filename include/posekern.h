@@ -159,7 +159,9 @@ int pk_spectral_diffusion(const float* in, int ld_in, const float* mass, const f
  * modeling/dpfm.py:185-193: C[b,i,:] = ((AAt_b + lambda diag(D_b[i,:]))^-1 BAt_b[i,:]^T)^T.
  * fp64 Gauss-Jordan with partial pivoting, one wave per (b, i). K must be 30.
  *   AAt, BAt, D, C: f32 [B,K,K]. Backward: G = dL/dC; dBAt f32 [B,K,K];
- *   dAAt_part f32 [B,K,K,K] per-row slabs -w_i x_i^T (dL/dAAt = sum over axis 1). */
+ *   dAAt_part f32 [B,K,K,K] per-row slabs -w_i x_i^T (dL/dAAt = sum over axis 1).
+ *   The backward requires a symmetric AAt: it solves w_i = M_i^-1 G[b,i,:] with the forward's
+ *   M_i (the general gradient needs M_i^-T); the forward takes any nonsingular M_i. */
 int pk_fmap_solve(const float* AAt, const float* BAt, const float* D, float lambda, int B, int K,
                   float* C, void* stream);
 int pk_fmap_solve_backward(const float* AAt, const float* BAt, const float* D, float lambda, int B,
