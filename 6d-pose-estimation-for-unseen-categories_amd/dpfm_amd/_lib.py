@@ -93,6 +93,9 @@ SIGNATURES = {
     "pk_overlap_head_bwd": [_P, _P],
     "pk_mlp3_fwd": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _I, _P, _P, _P, _I64, _I, _P],
     "pk_mlp3_bwd": [_P, _P, _P, _P, _P, _P, _I64, _I, _P, _P, _P, _P, _I, _P],
+    "pk_attn_mlp_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P],
+    "pk_attn_mlp_bwd_norm": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
+    "pk_attn_mlp_bwd_in": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
     "pk_resolvent_mask": [_P, _I, _P, _I, _I, _I, _F, _P, _P],
     "pk_linear_fwd": [_P, _P, _P, _I, _I64, _I, _I, _I, _I, _I, _P, _P, _P],
     "pk_feat_dist_work_size": [_I, _I, _I, _I, _I],

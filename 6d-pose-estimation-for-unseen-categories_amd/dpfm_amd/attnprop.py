@@ -14,13 +14,32 @@ backward, mlp.0^T, the merge^T reading its slice in place, the attention backwar
 into one stacked buffer, Pq^T with BOTH other contributions to d desc (the residual and the
 concatenation slice) added in its epilogue (add / add2), and [Pk; Pv]^T as one 64 -> 32 launch.
 Weight gradients go to the grouped launch (layers.GroupedWgrad) reading the stacked / sliced
-operands in place (pk_wgrad_call batch strides). Parameters and their names are the module's."""
+operands in place (pk_wgrad_call batch strides). Parameters and their names are the module's.
+
+At C = 32, unmasked, with rows of at most ops.ATTN_MLP_MAX_N points, the launches around the
+InstanceNorm are fused (ATTN_MLP_FUSE): forward, the copy + merge + mlp.0 + InstanceNorm/ReLU are
+one entry point (pk_attn_mlp_fwd: one launch when hc / h1 are not kept, else a per-point chain
+launch and the norm launch); backward, mlp.3^T + the norm backward are one (pk_attn_mlp_bwd_norm)
+and mlp.0^T + merge^T another (pk_attn_mlp_bwd_in). Every tensor is bit-identical either way."""
 from __future__ import annotations
+
+import os
 
 import torch
 
 from . import _lib, ops
 from ._lib import call, ptr
+
+
+# True: the fused launches of the MLP around the attention, both directions; "fwd" / "bwd": that
+# direction only; False (PK_ATTN_MLP_FUSE=0 at import): the per-layer launches.
+ATTN_MLP_FUSE = {"0": False, "fwd": "fwd", "bwd": "bwd"}.get(os.environ.get("PK_ATTN_MLP_FUSE", "1"), True)
+
+
+def _mlp_fused(direction: str, C: int, N: int, masked: bool) -> bool:
+    """Whether this call's MLP launches of `direction` ("fwd" / "bwd") take the fused kernels."""
+    return (ATTN_MLP_FUSE in (True, direction) and C == ops.ATTN_MLP_C and not masked
+            and N <= ops.ATTN_MLP_MAX_N)
 
 
 def _wgrad(x, dy, weight, bias):
@@ -33,8 +52,10 @@ def _wgrad(x, dy, weight, bias):
     return dw.view(weight.shape), db
 
 
-def _prop_fwd(x, src, P, heads, eps, nx=None, nsrc=None):
+def _prop_fwd(x, src, P, heads, eps, nx=None, nsrc=None, keep=True):
     """desc' = x + layer(x, src) in the launches above; returns (desc', saved tensors).
+    keep=False (no backward will run): the fused MLP launch does not store hc and h1, which only
+    the backward reads (they are None in the returned tuple).
     nx / nsrc (masked mode; int32 [B] on the device or None): the real points of x (the queries,
     and the rows the norm's statistics run over) and of src (the keys) — the attention and the norm
     then go to their varlen entry points; every other launch is per point. The `work=` figures
@@ -61,21 +82,28 @@ def _prop_fwd(x, src, P, heads, eps, nx=None, nsrc=None):
     else:
         call("pk_attention_fwd", ptr(q), ptr(kv), vptr, B, D, heads, N, M, 2 * C * M, 2 * C * M, ptr(a), ptr(lse),
              _lib.stream(dev), work=("mfma", 2 * 2 * N * M * D * B * heads))
-    hc = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)  # cat(desc, message)
-    call("pk_copy_rows", ptr(hc), 2 * C * N, ptr(x), C * N, B, C * N, _lib.stream(dev),
-         work=("hbm", 8 * B * C * N))
-    ops.linear_ex(a, f(wm), bm, 1, B * N, N, C, C, y=hc[:, C:], ldy=2 * C * N)
-    h1 = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
-    ops.linear_ex(hc, f(w0), b0, 1, B * N, N, 2 * C, 2 * C, y=h1)
-    h1n = torch.empty_like(h1)
+    h1n = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
     mean = torch.empty((B * 2 * C,), dtype=torch.float32, device=dev)
     invstd = torch.empty_like(mean)
-    if masked:
-        call("pk_instnorm_relu_fwd_varlen", ptr(h1), B * 2 * C, N, float(eps), ptr(h1n), ptr(mean), ptr(invstd),
-             2 * C, ptr(nx), _lib.stream(dev), work=("hbm", 8 * B * 2 * C * N))
+    hc = h1 = None
+    if _mlp_fused("fwd", C, N, masked):
+        if keep:
+            hc = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)  # cat(desc, message)
+            h1 = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
+        ops.attn_mlp_fwd(x, a, f(wm), bm, f(w0), b0, eps, h1n, mean, invstd, hc=hc, h1=h1)
     else:
-        call("pk_instnorm_relu_fwd", ptr(h1), B * 2 * C, N, float(eps), ptr(h1n), ptr(mean), ptr(invstd),
-             _lib.stream(dev), work=("hbm", 8 * B * 2 * C * N))
+        hc = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)  # cat(desc, message)
+        call("pk_copy_rows", ptr(hc), 2 * C * N, ptr(x), C * N, B, C * N, _lib.stream(dev),
+             work=("hbm", 8 * B * C * N))
+        ops.linear_ex(a, f(wm), bm, 1, B * N, N, C, C, y=hc[:, C:], ldy=2 * C * N)
+        h1 = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
+        ops.linear_ex(hc, f(w0), b0, 1, B * N, N, 2 * C, 2 * C, y=h1)
+        if masked:
+            call("pk_instnorm_relu_fwd_varlen", ptr(h1), B * 2 * C, N, float(eps), ptr(h1n), ptr(mean), ptr(invstd),
+                 2 * C, ptr(nx), _lib.stream(dev), work=("hbm", 8 * B * 2 * C * N))
+        else:
+            call("pk_instnorm_relu_fwd", ptr(h1), B * 2 * C, N, float(eps), ptr(h1n), ptr(mean), ptr(invstd),
+                 _lib.stream(dev), work=("hbm", 8 * B * 2 * C * N))
     out = torch.empty((B, C, N), dtype=torch.float32, device=dev)
     ops.linear_ex(h1n, f(w3), b3, 1, B * N, N, 2 * C, C, y=out, add=x, add_cols=C)
     return out, (x, src, q, kv, a, lse, hc, h1, h1n, mean, invstd)
@@ -92,24 +120,31 @@ def _prop_bwd(saved, P, heads, dout, dsrc_add=None, nx=None, nsrc=None):
     dev = x.device
     f = lambda w: w.view(w.shape[0], -1)  # noqa: E731
     dout = dout.contiguous()
-    # mlp.3 (its residual: dout flows to desc unchanged, added in Pq^T's epilogue below)
-    dh1n = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
-    ops.linear_ex(dout, f(w3), None, 1, B * N, N, C, 2 * C, y=dh1n, transw=True)
-    g_w3, g_b3 = _wgrad(h1n, dout, w3, b3)
-    dh1 = torch.empty_like(dh1n)
     masked = nx is not None or nsrc is not None  # (work= figures: padded shapes, as in _prop_fwd)
-    if masked:
-        call("pk_instnorm_relu_bwd_varlen", ptr(h1), ptr(dh1n), ptr(mean), ptr(invstd), B * 2 * C, N, ptr(dh1),
-             2 * C, ptr(nx), _lib.stream(dev), work=("hbm", 12 * B * 2 * C * N))
-    else:
-        call("pk_instnorm_relu_bwd", ptr(h1), ptr(dh1n), ptr(mean), ptr(invstd), B * 2 * C, N, ptr(dh1),
-             _lib.stream(dev), work=("hbm", 12 * B * 2 * C * N))
+    dh1 = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
     dhc = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
-    ops.linear_ex(dh1, f(w0), None, 1, B * N, N, 2 * C, 2 * C, y=dhc, transw=True)
-    g_w0, g_b0 = _wgrad(hc, dh1, w0, b0)
-    # merge^T on the message half of the concatenation gradient, read in place
     da = torch.empty((B, C, N), dtype=torch.float32, device=dev)
-    ops.linear_ex(dhc[:, C:], f(wm), None, 1, B * N, N, C, C, y=da, transw=True, ldx=2 * C * N)
+    if _mlp_fused("bwd", C, N, masked):
+        # mlp.3^T + the norm backward, then mlp.0^T + merge^T: two launches, dh1n never stored
+        ops.attn_mlp_bwd_norm(dout, f(w3), h1, mean, invstd, dh1)
+        g_w3, g_b3 = _wgrad(h1n, dout, w3, b3)
+        ops.attn_mlp_bwd_in(dh1, f(w0), f(wm), dhc, da)
+        g_w0, g_b0 = _wgrad(hc, dh1, w0, b0)
+    else:
+        # mlp.3 (its residual: dout flows to desc unchanged, added in Pq^T's epilogue below)
+        dh1n = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
+        ops.linear_ex(dout, f(w3), None, 1, B * N, N, C, 2 * C, y=dh1n, transw=True)
+        g_w3, g_b3 = _wgrad(h1n, dout, w3, b3)
+        if masked:
+            call("pk_instnorm_relu_bwd_varlen", ptr(h1), ptr(dh1n), ptr(mean), ptr(invstd), B * 2 * C, N, ptr(dh1),
+                 2 * C, ptr(nx), _lib.stream(dev), work=("hbm", 12 * B * 2 * C * N))
+        else:
+            call("pk_instnorm_relu_bwd", ptr(h1), ptr(dh1n), ptr(mean), ptr(invstd), B * 2 * C, N, ptr(dh1),
+                 _lib.stream(dev), work=("hbm", 12 * B * 2 * C * N))
+        ops.linear_ex(dh1, f(w0), None, 1, B * N, N, 2 * C, 2 * C, y=dhc, transw=True)
+        g_w0, g_b0 = _wgrad(hc, dh1, w0, b0)
+        # merge^T on the message half of the concatenation gradient, read in place
+        ops.linear_ex(dhc[:, C:], f(wm), None, 1, B * N, N, C, C, y=da, transw=True, ldx=2 * C * N)
     g_wm, g_bm = _wgrad(a, dhc[:, C:], wm, bm)
     # attention backward: dk / dv into one stacked buffer
     dq = torch.empty((B, C, N), dtype=torch.float32, device=dev)
@@ -148,7 +183,7 @@ class _AttnPropFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, src, wq, bq, wk, bk, wv, bv, wm, bm, w0, b0, w3, b3, heads, eps, nx=None, nsrc=None):
         P = (wq, bq, wk, bk, wv, bv, wm, bm, w0, b0, w3, b3)
-        out, saved = _prop_fwd(x, src, P, heads, eps, nx, nsrc)
+        out, saved = _prop_fwd(x, src, P, heads, eps, nx, nsrc, keep=any(ctx.needs_input_grad))
         ctx.heads = heads
         ctx.params = P
         ctx.lens = (nx, nsrc)  # (not differentiable, never outputs: plain attributes)
@@ -174,8 +209,9 @@ class _AttnPropPairFn(torch.autograd.Function):
         P = (wq, bq, wk, bk, wv, bv, wm, bm, w0, b0, w3, b3)
         # masked mode: the first call's queries are x0 (n0 real points) and its keys x1 (n1); the
         # second call's are reversed
-        out0, s0 = _prop_fwd(x0, x1, P, heads, eps, n0, n1)
-        out1, s1 = _prop_fwd(x1, out0, P, heads, eps, n1, n0)
+        keep = any(ctx.needs_input_grad)
+        out0, s0 = _prop_fwd(x0, x1, P, heads, eps, n0, n1, keep=keep)
+        out1, s1 = _prop_fwd(x1, out0, P, heads, eps, n1, n0, keep=keep)
         ctx.heads = heads
         ctx.params = P
         ctx.lens = (n0, n1)

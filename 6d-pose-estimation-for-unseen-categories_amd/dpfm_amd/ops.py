@@ -1016,6 +1016,43 @@ def mlp3_bwd(dy: torch.Tensor, h2: torch.Tensor, h1: torch.Tensor, w3, w2, w1, R
          work=("hbm", 4 * R * (3 * C + 2 * C + 2 * C) + _MLP3_WEIGHT_BYTES, 2 * R * C * 4 * C))
 
 
+ATTN_MLP_C = 32        # the fused attention-propagation MLP launches: channels
+ATTN_MLP_MAX_N = 2048  # and the longest (crop, channel) row pk_attn_mlp_fwd / _bwd_norm hold in LDS
+
+
+def attn_mlp_fwd(x: torch.Tensor, a: torch.Tensor, wm, bm, w0, b0, eps: float, h1n: torch.Tensor,
+                 mean: torch.Tensor, invstd: torch.Tensor, hc: Optional[torch.Tensor] = None,
+                 h1: Optional[torch.Tensor] = None) -> None:
+    """pk_attn_mlp_fwd: hc = cat(x, Wm a + bm), h1 = W0 hc + b0, h1n = relu(instnorm(h1)) in one
+    launch (two when hc and h1 are both stored: the per-point chain, then the norm); x, a [B, 32, N], hc / h1 / h1n [B, 64, N], mean / invstd [B * 64]. hc and h1 are stored
+    only when given (the backward's operands)."""
+    B, C, N = x.shape
+    kept = (hc is not None) + (h1 is not None)
+    call("pk_attn_mlp_fwd", ptr(x), ptr(a), ptr(wm), ptr(bm), ptr(w0), ptr(b0), B, C, N, float(eps), ptr(hc), ptr(h1),
+         ptr(h1n), ptr(mean), ptr(invstd), _lib.stream(x.device),
+         work=("hbm", 4 * B * N * (2 * C + 2 * C + kept * 2 * C) + 4 * (5 * C * C + 3 * C) + 8 * B * 2 * C,
+               2 * B * N * (C * C + 4 * C * C)))
+
+
+def attn_mlp_bwd_norm(dout: torch.Tensor, w3, h1: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor,
+                      dh1: torch.Tensor) -> None:
+    """pk_attn_mlp_bwd_norm: dh1 = instnorm_relu_bwd(h1, W3^T dout, mean, invstd) in one launch;
+    dout [B, 32, N], h1 / dh1 [B, 64, N]."""
+    B, C, N = dout.shape
+    call("pk_attn_mlp_bwd_norm", ptr(dout), ptr(w3), ptr(h1), ptr(mean), ptr(invstd), B, C, N, ptr(dh1),
+         _lib.stream(dout.device),
+         work=("hbm", 4 * B * N * (C + 2 * C + 2 * C) + 4 * 2 * C * C + 8 * B * 2 * C, 2 * B * N * 2 * C * C))
+
+
+def attn_mlp_bwd_in(dh1: torch.Tensor, w0, wm, dhc: torch.Tensor, da: torch.Tensor) -> None:
+    """pk_attn_mlp_bwd_in: dhc = W0^T dh1 and da = Wm^T dhc[:, 32:] in one launch; dh1 / dhc
+    [B, 64, N], da [B, 32, N]."""
+    B, C2, N = dh1.shape
+    C = C2 // 2
+    call("pk_attn_mlp_bwd_in", ptr(dh1), ptr(w0), ptr(wm), B, C, N, ptr(dhc), ptr(da), _lib.stream(dh1.device),
+         work=("hbm", 4 * B * N * (2 * C + 2 * C + C) + 4 * 5 * C * C, 2 * B * N * (4 * C * C + C * C)))
+
+
 def linear_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], channels_first: bool,
                transw: bool = False, relu: bool = False, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """pk_linear_fwd: y = x W^T (+ b) over every point (W [Cout, Cin], or W^T read from a

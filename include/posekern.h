@@ -360,6 +360,27 @@ int pk_mlp3_fwd(const float* x_in, int64_t ld_in, const float* x_diff, int64_t l
 int pk_mlp3_bwd(const float* dy, const float* h2, const float* h1, const float* w3, const float* w2, const float* w1,
                 int64_t R, int C, float* d2, float* d1, float* dx, float* dd, int max_blocks, void* stream);
 
+/* H8 the MLP around the cross-attention of one AttentionalPropagation call (modeling/dpfm.py:45-82)
+ * in three launches; C = 32, channels-first f32 [B, C, N] / [B, 2C, N] contiguous, N <= 2048 (16
+ * rows of the norm in LDS, each in one wave's registers) for the first two. Every output is
+ * bit-identical to the pk_copy_rows / pk_linear_ex / pk_instnorm_relu_* launches it replaces.
+ *   pk_attn_mlp_fwd       message = Wm a + bm; hc = cat(x, message) [B, 2C, N]; h1 = W0 hc + b0;
+ *                         h1n = relu((h1 - mean) invstd) with mean / invstd [B * 2C] over each
+ *                         (crop, channel) row (biased variance, eps). Wm [C, C], W0 [2C, 2C] 16-B
+ *                         aligned. hc and h1 may be NULL (not stored: no backward will read them).
+ *                         With both given: a per-point launch for hc / h1, then pk_instnorm_relu_fwd
+ *                         on h1; otherwise one launch, the 16 rows of a workgroup normalised in LDS.
+ *   pk_attn_mlp_bwd_norm  dh1 = instnorm_relu_bwd(h1, W3^T dout, mean, invstd); dout [B, C, N],
+ *                         W3 [C, 2C]. The gradient in between (dh1n) is not written.
+ *   pk_attn_mlp_bwd_in    dhc = W0^T dh1 [B, 2C, N] (all rows); da = Wm^T dhc[:, C:] [B, C, N]; any N. */
+int pk_attn_mlp_fwd(const float* x, const float* a, const float* wm, const float* bm, const float* w0,
+                    const float* b0, int B, int C, int N, float eps, float* hc, float* h1, float* h1n, float* mean,
+                    float* invstd, void* stream);
+int pk_attn_mlp_bwd_norm(const float* dout, const float* w3, const float* h1, const float* mean, const float* invstd,
+                         int B, int C, int N, float* dh1, void* stream);
+int pk_attn_mlp_bwd_in(const float* dh1, const float* w0, const float* wm, int B, int C, int N, float* dhc, float* da,
+                       void* stream);
+
 /* H9 fmap head around the solve (modeling/dpfm.py:154-176, models/dpfm.py:66-72), K = 30,
  * C = 32: W = evecs[:, :K] * mass (f32 products); A = W_x^T F_x, Bm = W_y^T F_y [B,K,C];
  * AAt = A A^T, BAt = Bm A^T [B,K,K]; D = get_mask(evals_x[:K], evals_y[:K], gamma) [B,K,K].
