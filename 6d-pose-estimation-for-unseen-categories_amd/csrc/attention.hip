@@ -32,11 +32,12 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
+using pk::f32x2;
+using pk::f32x4;
 constexpr int kD = 16;       // head dim
 constexpr int kT = 64;       // rows per tile / per workgroup
 constexpr float kScale = 0.25f;  // 1 / sqrt(dim) for the gradients

@@ -13,7 +13,7 @@
 // computes those 16 complete rows into LDS (16 x N floats) and normalises them there. The backward
 // mirrors it: mlp.3^T gives complete dh1n rows per (crop, 16 channels) for the norm backward.
 //
-// Every element is bit-identical to the per-layer launches (linear_cf_body in linear.hip and
+// Every element is bit-identical to the per-layer launches (linear_cf_body in linear_fwd.hip and
 // instnorm_relu_*_kernel in norm.hip): the products run on v_mfma_f32_16x16x4f32 with the weight
 // as the A operand and the points as the B operand, contraction channel 16 q + 4 g + i on lane
 // group g at step (q outer, i inner), the bias added after the accumulation (a null bias adds
@@ -28,21 +28,19 @@
 // vector per channel (SUB > 1 needs N % (16 SUB) == 0; with SUB = 1 a crop's last tile may be
 // ragged: its columns past N compute on a clamped point and are not stored).
 #include "common.hpp"
+#include "mfma_tile.hpp"
 #include "../../include/posekern.h"
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
+using pk::f32x2;
+using pk::f32x4;
+using pk::PtVec;  // SUB points of one channel per lane
+using pk::al16;
 
 constexpr int kC = 32;          // channels of the refinement (heads x 16)
 constexpr int kMaxN = 2048;     // the norm's register tile (64 lanes x 32), 16 rows = 128 KB of LDS
 constexpr int kRowWaves = 8;    // waves of a row-owning workgroup (2 of its 16 rows each in the norm)
-
-template <int SUB> struct PtVec;
-template <> struct PtVec<1> { using T = float; };
-template <> struct PtVec<2> { using T = f32x2; };
-template <> struct PtVec<4> { using T = f32x4; };
 
 template <int SUB>
 __device__ __forceinline__ float vget(const typename PtVec<SUB>::T& v, int u) {
@@ -455,8 +453,6 @@ __global__ __launch_bounds__(256) void attn_mlp_bwd_in_kernel(const float* __res
       if (live) *reinterpret_cast<V*>(ob + (int64_t)(16 * t + 4 * g + r) * N) = v;
     }
 }
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

@@ -20,6 +20,7 @@
 //   3. compaction         : ordered pair list (i, j) int64 [B, cap, 2] + overlaps.
 // pk_ball_query_pairs chains 2 and 3 after 1 (or recomputes distances if no mask).
 #include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace {
 
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(kBqThreads) void bq_mask_f32_kernel(
 // of (|a|^2 + |b|^2) by one rounding of (lo - |a|^2), covered by the 2u*thr2 term.
 constexpr int kStageCols = 2048;  // columns converted into LDS per stage (32 KiB)
 using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
+using pk::f32x2;
 
 __device__ __forceinline__ float next_up(float x) {  // nextafter(x, +inf) for finite x
   const uint32_t b = __float_as_uint(x);

@@ -7,10 +7,11 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using pk::f32x4;
 constexpr int kPer = 4;  // float4s per thread
 
 __global__ __launch_bounds__(256) void copy_rows_v4_kernel(float* __restrict__ dst, int64_t ld_dst,

@@ -10,10 +10,11 @@
 //           resident weight, one barrier) before the tile is consumed
 //   mode 3  mode 1 with 16-B stores (a lane owns 4 consecutive outputs of one row)
 #include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using pk::f32x4;
 
 __global__ __launch_bounds__(256) void probe_linear_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                            int64_t R) {

@@ -35,6 +35,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace {
 
@@ -44,7 +45,7 @@ constexpr int kCW = 1;   // column tiles per wave
 constexpr int kWaves = 4;
 constexpr int kCols = kWaves * kCW * 16;  // columns per block
 constexpr int kCH = 8;   // row tiles per LDS stage
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using pk::f32x4;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 

@@ -18,7 +18,7 @@
 //   pk_gradfeat_fwd   g = tanh(vX . B_re + vY . B_im), [B_re | B_im] = [vX | vY] x the stacked
 //                     128 x 128 rotation weight [[A_re^T, A_im^T], [-A_im^T, A_re^T]] on
 //                     v_mfma_f32_32x32x2_f32: one wave = 32 points x 128 outputs (four 32 x 32
-//                     accumulators); the lane halves split the contraction as in linear.hip — half 0
+//                     accumulators); the lane halves split the contraction as in linear_fwd.hip — half 0
 //                     holds the point's vX row, half 1 its vY row, so MFMA step s contracts the pair
 //                     (vX[s], vY[s]) against rows (A_re[:, s], -A_im[:, s]) / (A_im[:, s], A_re[:, s])
 //                     read from one LDS copy of A_re and A_im (the stacked matrix is never built).
@@ -30,11 +30,14 @@
 //   pk_linear192_fwd  the block's first MLP layer on 192 inputs (pk_linear_ex stops at 128): the
 //                     same 32-points-per-wave product with 96 contraction steps per lane half.
 #include "common.hpp"
+#include "mfma_tile.hpp"
 #include "posekern.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using pk::f32x16;
+using pk::al16;
+using pk::al8;
 
 constexpr int kGfC = 64;
 constexpr int kGfST = kGfC + 1;          // LDS row stride of a 64 x 64 weight (odd: conflict-free both ways)
@@ -322,9 +325,6 @@ __global__ __launch_bounds__(256) void linear192_kernel(const float* __restrict_
     }
   }
 }
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 }  // namespace
 

@@ -10,6 +10,7 @@
 // expand (Phi · coefficients [· m]). Layout: x / y [B, N, C], Phi [B, N, K] row-major,
 // m [B, N], lambda [B, K], t [C]; N is the padded per-crop point count.
 #include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace {
 
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(256) void spec_expand_kernel(const float* __restric
 // Lane map as in attention.hip: A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15],
 // D[4 (l >> 4) + rr][l & 15]. Every lane loads whole float4s of a row, and the matrix indices are
 // permuted to match (documented per kernel), so no operand goes through LDS shuffles.
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using pk::f32x4;
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);

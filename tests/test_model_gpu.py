@@ -836,3 +836,58 @@ def test_linear_ex2_pair_matches_two_calls(device, N):
         assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]), (ci0, co0, ci1, co1)
         ref0 = torch.einsum("oi,bin->bon", w0.cpu(), x0.cpu()) + b0.cpu()[None, :, None] + add0.cpu() + add20.cpu()
         assert (outs[1][0] - ref0).abs().max().item() <= 1e-4 * ref0.abs().max().item()
+
+
+def test_linear_ex_rejects_like_pair(device):
+    """pk_linear_ex and pk_linear_ex2 share one set of argument checks: every malformed call is
+    refused with "invalid argument" by both entry points — alone, first of a pair and second of a
+    pair next to a valid partner — before anything is launched (the NaN-filled outputs of the bad
+    call and of its partner stay NaN). R = 0 is valid and touches no output on either entry."""
+    from dpfm_amd import _lib, ops
+    R = 32
+
+    def z(*s):
+        return torch.zeros(*s, device=device)
+
+    def nan(*s):
+        return torch.full(s, float("nan"), device=device)
+
+    def mk(layout=0, N=0, Cin=32, Cout=32, R=R, **kw):
+        y = nan(R, Cout)
+        args = (z(R, Cin), z(Cout, Cin), z(Cout), layout, R, N, Cin, Cout, y)
+        return args, kw, [y] + [kw[k] for k in ("y2", "pre_out") if k in kw]
+
+    bad = {
+        "layout = 2": mk(layout=2),
+        "Cin = 129": mk(Cin=129),
+        "act = 3": mk(act=3),
+        "channels-first, R % N != 0": mk(layout=1, N=5),
+        "y2 with split = Cout": mk(y2=nan(R, 32), split=32),
+        "y2 with layout = 1": mk(layout=1, N=R, y2=nan(R, 16), split=16),
+        "add with add_cols = 0": mk(add=z(R, 32), add_cols=0),
+        "w2 with layout = 0": mk(w2=z(16, 32), wsplit=16),
+        "w2 with wsplit = 0": mk(layout=1, N=R, w2=z(16, 32), wsplit=0),
+        "bias2 without w2": mk(layout=1, N=R, bias2=z(16)),
+        "pre with Cin = Cout = 32": mk(pre=z(R, 32)),
+    }
+    for name, (args, kw, outs) in bad.items():
+        with pytest.raises(_lib.PoseKernError, match="invalid argument"):
+            ops.linear_ex(*args, **kw)
+        for bad_first in (True, False):
+            pa, pkw, pouts = mk(Cin=16, Cout=16)  # a valid rows-layout partner
+            with pytest.raises(_lib.PoseKernError, match="invalid argument"):
+                if bad_first:
+                    ops.linear_ex2(args, kw, pa, pkw)
+                else:
+                    ops.linear_ex2(pa, pkw, args, kw)
+            outs = outs + pouts
+        torch.cuda.synchronize()
+        assert all(bool(torch.isnan(o).all()) for o in outs), name
+    # no rows: a valid call that returns before touching y (the data pointers are never read)
+    for layout, N in [(0, 0), (1, 8)]:
+        args, kw, outs = mk(layout=layout, N=N)
+        args = args[:4] + (0,) + args[5:]
+        ops.linear_ex(*args, **kw)
+        ops.linear_ex2(args, kw, args, kw)
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(outs[0]).all()), (layout, N)
