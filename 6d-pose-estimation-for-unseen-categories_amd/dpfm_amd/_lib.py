@@ -110,6 +110,7 @@ SIGNATURES = {
     "pk_ransac_work_size": [_I, _I64, _I],
     "pk_ransac": [_P, _P, _P, _P, _P, _P, _P, _P, _U64, _I64, _D, _I, _I, _P, _I64, _P, _P, _P, _P],
     "pk_pose_metrics": [_P, _P, _I, _I, _P, _P, _P, _P, _P],
+    "pk_bop_errors": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "pk_erode_mask": [_P, _I, _I, _I, _P, _P],
     "pk_sample_rgb": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P],
     "pk_sample_features": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P],

@@ -259,15 +259,52 @@ def _models_info(models_dir: str) -> dict:
         return json.load(f)
 
 
+def _axis_rotation(angle: float, axis) -> np.ndarray:
+    """Rotation by `angle` about the unit vector along `axis` (Rodrigues); angle 0 is exactly I."""
+    a = np.asarray(axis, dtype=np.float64).reshape(3)
+    a = a / np.linalg.norm(a)
+    c, s = np.cos(angle), np.sin(angle)
+    ax = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return c * np.eye(3) + s * ax + (1.0 - c) * np.outer(a, a)
+
+
+def symmetry_transformations(model_info: dict, max_sym_disc_step: float = 0.01, scale: float = 0.1) -> np.ndarray:
+    """The symmetry set of one models_info.json entry as f64 [S, 4, 4] (absent in the reference;
+    restated from bop_toolkit misc.get_symmetry_transformations): the identity followed by every
+    `symmetries_discrete` 16-vector, combined with every `symmetries_continuous` (axis, offset)
+    discretised into n = ceil(pi / max_sym_disc_step) rotations by 2 pi i / n, i = 0 .. n - 1, about
+    the axis through the offset — for each discrete D, for each continuous C: C D. i = 0 is kept,
+    so element 0 is always the identity (bop_toolkit starts at i = 1 and lists it once).
+    Translations are multiplied by `scale` (0.1: mm -> cm, as object_frame scales the CAD)."""
+    disc = [np.eye(4)]
+    for d in model_info.get("symmetries_discrete", []):
+        disc.append(np.asarray(d, dtype=np.float64).reshape(4, 4))
+    cont = []
+    n = int(np.ceil(np.pi / max_sym_disc_step))
+    for c in model_info.get("symmetries_continuous", []):
+        off = np.asarray(c["offset"], dtype=np.float64).reshape(3)
+        for i in range(n):
+            T = np.eye(4)
+            T[:3, :3] = _axis_rotation(2.0 * np.pi * i / n, c["axis"])
+            T[:3, 3] = off - T[:3, :3] @ off
+            cont.append(T)
+    out = np.stack([C @ D for D in disc for C in cont] if cont else disc)
+    out[:, :3, 3] *= scale
+    out[:, 3, :] = (0.0, 0.0, 0.0, 1.0)
+    return out
+
+
 _CAD_CACHE: dict = {}  # (models_dir, obj_id) -> vertices * 0.1: a PLY is parsed once per process
 
 
-def object_frame(scenes: BopScenes, i: int, j: int, models_dir, cad_cache: Optional[dict] = None) -> dict:
+def object_frame(scenes: BopScenes, i: int, j: int, models_dir, cad_cache: Optional[dict] = None,
+                 symmetries: bool = False) -> dict:
     """The fields dataset/object.py:133-164 derives for (frame i, object j), as the dict
     `pipeline.frame_batch` packs: depth, mask (mask_visib == 255 test done by the crop kernels
     on value 255), K, depth_scale, R_m2c, t_m2c (* 0.1: cm), cad (model vertices * 0.1 —
     the reference decimates the mesh to 10k faces with Open3D first, :199; out of scope here,
-    pass a decimated vertex set through `cad_cache` to reproduce it), diam_cad (* 0.1)."""
+    pass a decimated vertex set through `cad_cache` to reproduce it), diam_cad (* 0.1).
+    symmetries=True adds "syms": the object's symmetry_transformations (the default dict is unchanged)."""
     sc = scenes[i]
     gt = sc["scene_gt"][j]
     oid = int(gt["obj_id"])
@@ -282,13 +319,16 @@ def object_frame(scenes: BopScenes, i: int, j: int, models_dir, cad_cache: Optio
             cad_cache[oid] = read_ply(models_dir / f"obj_{oid:06d}.ply").vertices * 0.1
         cad = cad_cache[oid]
     info = _models_info(str(models_dir.resolve()))
-    return {"depth": sc["depth"], "mask": sc["seg"][j], "K": np.asarray(sc["camera"]["cam_K"], np.float64).reshape(3, 3),
-            "depth_scale": float(sc["camera"]["depth_scale"]),
-            "R_m2c": np.asarray(gt["cam_R_m2c"], np.float64).reshape(3, 3),
-            "t_m2c": np.asarray(gt["cam_t_m2c"], np.float64) * 0.1, "obj_id": oid,
-            "visib_fract": float(sc["scene_info"][j]["visib_fract"]),
-            "cad": cad, "diam_cad": float(info[str(oid)]["diameter"]) * 0.1,
-            "rgb": sc.get("color")}
+    out = {"depth": sc["depth"], "mask": sc["seg"][j], "K": np.asarray(sc["camera"]["cam_K"], np.float64).reshape(3, 3),
+           "depth_scale": float(sc["camera"]["depth_scale"]),
+           "R_m2c": np.asarray(gt["cam_R_m2c"], np.float64).reshape(3, 3),
+           "t_m2c": np.asarray(gt["cam_t_m2c"], np.float64) * 0.1, "obj_id": oid,
+           "visib_fract": float(sc["scene_info"][j]["visib_fract"]),
+           "cad": cad, "diam_cad": float(info[str(oid)]["diameter"]) * 0.1,
+           "rgb": sc.get("color")}
+    if symmetries:  # f64 [S, 4, 4] in cm (pipeline.frame_batch packs it for InferStep(bop_metrics=True))
+        out["syms"] = symmetry_transformations(info[str(oid)])
+    return out
 
 
 # --------------------------------------------------------------------------- operator caches

@@ -135,6 +135,10 @@ class FrameBatch:
     max_pixels: int          # host bound on mask pixels per frame (kernel grid sizing)
     thr2: torch.Tensor       # f64 [F] ball-query threshold T(0.05 * diam) (ops.ball_threshold)
     n1max: int = 0           # largest CAD (collate's padded CAD length)
+    # object symmetry sets for the BOP errors (formats.symmetry_transformations), packed; None: identity only
+    syms: Optional[torch.Tensor] = None     # f64 [sum S_f, 4, 4]
+    sym_off: Optional[torch.Tensor] = None  # int64 [F + 1]
+    smax: int = 0                           # largest set (host)
 
 
 @dataclass

@@ -1812,6 +1812,49 @@ def pose_metrics(cad: torch.Tensor, off: torch.Tensor, nmax: int, T_est: torch.T
     return out
 
 
+# pk_bop_errors' tiling (include/posekern.h PK_BOP_*): the sizes at which its kernels change path
+BOP_QUERY_BLOCK, BOP_TARGET_TILE, BOP_SYM_CHUNK = 512, 1024, 8
+
+
+def bop_errors_work_len(B: int, nmax: int, smax: int) -> int:
+    """f64 elements of pk_bop_errors' scratch (the formula of include/posekern.h)."""
+    return int(B) * (4 * int(nmax) + 2 * max(int(smax), 1))
+
+
+def bop_errors(cad: torch.Tensor, off: torch.Tensor, nmax: int, T_est: torch.Tensor, T_gt: torch.Tensor,
+               K: Optional[torch.Tensor] = None, sym: Optional[torch.Tensor] = None,
+               sym_off: Optional[torch.Tensor] = None, smax: Optional[int] = None):
+    """pk_bop_errors -> (out f64 [B, 3] = (MSSD, MSPD, ADI), best int32 [B, 2] = the symmetry index
+    of the MSSD and of the MSPD minimum). K f64 [B, 3, 3] (None: MSPD is NaN, best[:, 1] = -1);
+    sym f64 [S_total, 4, 4] with sym_off int64 [B + 1] (None: the identity alone). smax bounds the
+    largest per-crop set (host knowledge); by default S_total, which always holds. No host read."""
+    assert cad.dtype == torch.float64 and T_est.dtype == torch.float64 and T_gt.dtype == torch.float64
+    B = off.numel() - 1
+    dev = cad.device
+    nmax = int(nmax)
+    if sym is None:
+        smax, sym_off = 1, None
+    else:
+        if sym_off is None:
+            raise ValueError("bop_errors: sym needs sym_off")
+        assert sym.dtype == torch.float64 and sym_off.dtype == torch.int64 and sym_off.numel() == B + 1
+        sym = sym.reshape(-1, 4, 4).contiguous()
+        smax = max(int(sym.shape[0] if smax is None else smax), 1)
+    if K is not None:
+        assert K.dtype == torch.float64 and K.numel() == 9 * B
+        K = K.contiguous()
+    out = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    best = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    if B == 0 or nmax <= 0:  # the entry point touches nothing: no crop can be evaluated
+        return out.fill_(float("nan")), best.fill_(-1)
+    work = torch.empty((bop_errors_work_len(B, nmax, smax),), dtype=torch.float64, device=dev)
+    npts = int(cad.shape[0])
+    call("pk_bop_errors", ptr(cad), ptr(off), B, nmax, ptr(T_est.contiguous()), ptr(T_gt.contiguous()), ptr(K),
+         ptr(sym), ptr(sym_off), smax, ptr(work), ptr(out), ptr(best), _lib.stream(dev),
+         work=("valu64", 9 * npts * max(npts // B, 1)))  # ADI: 9 flop per pair, equal-size crops assumed
+    return out, best
+
+
 def erode_mask(mask: torch.Tensor) -> torch.Tensor:
     F_, H, W = mask.shape
     out = torch.empty_like(mask)

@@ -138,7 +138,8 @@ def frame_batch(frames: list, device) -> FrameBatch:
     (dataset/scene.py:125-158, object.py:133-164): depth uint16 [H, W], mask uint8 [H, W]
     (mask_visib, 255 = object), K [3, 3], depth_scale, R_m2c [3, 3], t_m2c [3] (cm), cad f64
     [n1, 3] (cm, the decimated CAD vertices; ragged across frames), diam_cad (cm); rgb uint8
-    [H, W, 3] optional."""
+    [H, W, 3] optional; syms f64 [S, 4, 4] optional (formats.object_frame(symmetries=True)), packed
+    into FrameBatch.syms / sym_off when any frame carries one."""
     d = torch.device(device)
     st = lambda key, dt: torch.as_tensor(np.stack([np.asarray(f[key], dtype=dt) for f in frames]), device=d)  # noqa
     H, W = np.asarray(frames[0]["depth"]).shape[:2]
@@ -146,7 +147,14 @@ def frame_batch(frames: list, device) -> FrameBatch:
            for f in frames]
     cads = [np.asarray(f["cad"], dtype=np.float64).reshape(-1, 3) for f in frames]
     diam = [float(f["diam_cad"]) for f in frames]
+    sym_kw = {}
+    if any(f.get("syms") is not None for f in frames):  # a frame without a set gets the identity
+        sets = [np.asarray(f["syms"], dtype=np.float64).reshape(-1, 4, 4) if f.get("syms") is not None
+                else np.eye(4)[None] for f in frames]
+        sym_kw = dict(syms=torch.as_tensor(np.concatenate(sets, 0), device=d),
+                      sym_off=ops.packed_offsets([len(s) for s in sets], d), smax=max(len(s) for s in sets))
     return FrameBatch(
+        **sym_kw,
         depth=torch.as_tensor(np.stack([np.asarray(f["depth"], dtype=np.uint16).view(np.int16) for f in frames]),
                               device=d),
         mask=st("mask", np.uint8), rgb=torch.as_tensor(np.stack(rgb), device=d),
@@ -676,14 +684,18 @@ class InferStep:
 
     def __init__(self, model: DPFMNet, hypotheses: int = 1024, seed: int = 0, max_dist: float = 0.05,
                  icp_evaluations: int = 0, icp_threshold: float = 0.2, masked: bool = False,
-                 icp_estimation: str = "point_to_point"):
+                 icp_estimation: str = "point_to_point", bop_metrics: bool = False):
         """icp_evaluations > 0 refines each RANSAC pose by point-to-point ICP of the CAD against the
         observed crop (test_RANSAC.py:436-446 runs ICP after RANSAC, against the GT-posed CAD; the
         crop is the target available without ground truth), with that many evaluations enqueued
         (capturable: no host read) and the metrics also reported for the refined pose.
         icp_estimation="point_to_plane": the crop's normals are estimated inside the step (30
         neighbours, oriented towards the camera at the origin) and the ICP update is Open3D's
-        TransformationEstimationPointToPlane."""
+        TransformationEstimationPointToPlane.
+        bop_metrics=True adds the BOP pose errors of the same T / T_gt / fb.K with the frame batch's
+        symmetry sets (ops.bop_errors): `bop` f64 [B, 3] = (MSSD, MSPD, ADI), `bop_best` int32 [B, 2],
+        and `bop_icp` for the refined pose when ICP is on. Off: the output dict is unchanged."""
+        self.bop_metrics = bool(bop_metrics)
         if icp_estimation not in ops.ICP_ESTIMATIONS:
             raise ValueError(f"icp_estimation must be one of {ops.ICP_ESTIMATIONS}, got {icp_estimation!r}")
         self.model, self.H, self.seed, self.max_dist = model, hypotheses, seed, max_dist
@@ -757,6 +769,12 @@ class InferStep:
                                              estimation=self.icp_estimation)
             out.update(T_icp=T_icp, icp=icp_stats,
                        metrics_icp=ops.pose_metrics(fb.cad64, fb.cad_off, n1cap, T_icp, T_gt))
+        if self.bop_metrics:
+            bop = lambda Te: ops.bop_errors(fb.cad64, fb.cad_off, n1cap, Te, T_gt, fb.K, fb.syms, fb.sym_off,  # noqa: E731
+                                            fb.smax or None)
+            out["bop"], out["bop_best"] = bop(T)
+            if self.icp_evaluations > 0:
+                out["bop_icp"] = bop(out["T_icp"])[0]
         return out
 
 

@@ -603,6 +603,39 @@ int pk_ransac(const double* src, const int64_t* src_off, const double* dst, cons
 int pk_pose_metrics(const double* cad, const int64_t* off, int B, int nmax, const double* T_est,
                     const double* T_gt, double* work, double* out, void* stream);
 
+/* BOP pose errors with object symmetry sets (absent in the reference; restated from bop_toolkit
+ * pose_error.py mssd / mspd / adi, with the symmetry sets of misc.get_symmetry_transformations)
+ * for B crops, fp64 throughout:
+ *   MSSD = min_S max_x ||T_est x - T_gt S x||
+ *   MSPD = min_S max_x ||proj(K, T_est x) - proj(K, T_gt S x)||  (pixels),
+ *          proj(K, p) = ((K p)_0 / (K p)_2, (K p)_1 / (K p)_2)
+ *   ADI  = mean_x min_y ||T_est x - T_gt y|| over the crop's own vertices (no symmetry set)
+ *   cad f64 [T,3] packed / off (model points in the object frame), nmax = the scratch capacity
+ *   T_est / T_gt f64 [B,4,4] row-major (the last row is not read)
+ *   K f64 [B,3,3] row-major, or NULL: the MSPD column is NaN and best[:,1] = -1
+ *   sym f64 [S_total,4,4] row-major rigid transforms (the last row is not read), the set of crop b
+ *   being rows [sym_off[b], sym_off[b+1]) (sym_off int64 [B+1], device), smax >= the largest set;
+ *   sym NULL: every crop's set is the identity alone (sym_off and smax are not read)
+ *   work f64 [B * (4 * nmax + 2 * max(smax, 1))] scratch (T_gt y as [B,3,nmax], the per-query
+ *   minima [B,nmax], the per-symmetry maxima [B,smax,2]); nothing is kept across calls
+ *   out f64 [B,3] = (MSSD, MSPD, ADI); best int32 [B,2] = (argmin S of MSSD, argmin S of MSPD),
+ *   an exact tie going to the lowest index.
+ * A crop with 0 points, with more than nmax points, or with a non-finite entry in T_est is not
+ * evaluated: its row is NaN and its best (-1, -1); the other crops are unaffected. A crop whose
+ * symmetry count lies outside [1, smax] reports NaN / -1 in the MSSD and MSPD columns only.
+ * B == 0 or nmax == 0: returns 0 and touches nothing. Sizes are read from off / sym_off on the
+ * device (no host synchronisation: capturable). No floating-point atomics; every reduction runs
+ * in a fixed order, so results are bit-identical from run to run.
+ * Tiling (the sizes at which the kernels change path; tests/test_bop_metrics_gpu.py walks them):
+ * the ADI workgroup takes PK_BOP_QUERY_BLOCK queries and streams the transformed targets through
+ * LDS in tiles of PK_BOP_TARGET_TILE; the MSSD / MSPD workgroup takes PK_BOP_SYM_CHUNK symmetries. */
+#define PK_BOP_QUERY_BLOCK 512
+#define PK_BOP_TARGET_TILE 1024
+#define PK_BOP_SYM_CHUNK 8
+int pk_bop_errors(const double* cad, const int64_t* off, int B, int nmax, const double* T_est,
+                  const double* T_gt, const double* K, const double* sym, const int64_t* sym_off, int smax,
+                  double* work, double* out, int32_t* best, void* stream);
+
 /* erode_seg_mask alone (dataset/object.py:52-71): plus-shaped 3x3 erosion of
  * `mask == 255`, border pixels not eroded by the image edge. out uint8 [F,H,W] 0/1. */
 int pk_erode_mask(const uint8_t* mask, int F, int H, int W, uint8_t* out, void* stream);
