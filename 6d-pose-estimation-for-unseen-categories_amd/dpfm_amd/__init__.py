@@ -9,6 +9,9 @@ Module layout mirrors the reference so call sites read the same:
   pose/                                   RANSAC + Umeyama pose fit, ADD metrics
   dpfm_utils.py                           upstream DPFM helpers (FPS, get_mask, WBCE)
   ops.py                                  torch front-ends of libposekern.so (C-ABI)
+  wgrad.py                                weight gradients of the hand-written backwards: computed
+                                          per layer, or recorded for the step's grouped launch
+  layers.py, attnprop.py, overlap_head.py the per-point layers and the fused refinement / head nodes
 """
 __version__ = "0.1.0"
 

@@ -13,7 +13,7 @@ InstanceNorm+ReLU and mlp.3 with the residual in its epilogue; backward: mlp.3^T
 backward, mlp.0^T, the merge^T reading its slice in place, the attention backward writing dk / dv
 into one stacked buffer, Pq^T with BOTH other contributions to d desc (the residual and the
 concatenation slice) added in its epilogue (add / add2), and [Pk; Pv]^T as one 64 -> 32 launch.
-Weight gradients go to the grouped launch (layers.GroupedWgrad) reading the stacked / sliced
+Weight gradients go to the grouped launch (wgrad.GroupedWgrad) reading the stacked / sliced
 operands in place (pk_wgrad_call batch strides). Parameters and their names are the module's.
 
 At C = 32, unmasked, with rows of at most ops.ATTN_MLP_MAX_N points, the launches around the
@@ -29,6 +29,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import call, ptr
+from .wgrad import weight_grad
 
 
 # True: the fused launches of the MLP around the attention, both directions; "fwd" / "bwd": that
@@ -42,24 +43,13 @@ def _mlp_fused(direction: str, C: int, N: int, masked: bool) -> bool:
             and N <= ops.ATTN_MLP_MAX_N)
 
 
-def _wgrad(x, dy, weight, bias):
-    """(dW, db) through the active GroupedWgrad, or computed here (None, None when recorded)."""
-    from . import layers
-    if layers._side_owns(weight, bias):
-        layers._SIDE.launch(x, dy, weight, bias, channels_first=True)
-        return None, None
-    dw, db = ops.linear_wgrad(x, dy, channels_first=True, want_bias=bias is not None)
-    return dw.view(weight.shape), db
-
-
 def _prop_fwd(x, src, P, heads, eps, nx=None, nsrc=None, keep=True):
     """desc' = x + layer(x, src) in the launches above; returns (desc', saved tensors).
     keep=False (no backward will run): the fused MLP launch does not store hc and h1, which only
     the backward reads (they are None in the returned tuple).
     nx / nsrc (masked mode; int32 [B] on the device or None): the real points of x (the queries,
     and the rows the norm's statistics run over) and of src (the keys) — the attention and the norm
-    then go to their varlen entry points; every other launch is per point. The `work=` figures
-    keep the padded shapes in masked mode (an upper bound: the lengths live on the device)."""
+    then go to their varlen entry points (ops.*_raw); every other launch is per point."""
     wq, bq, wk, bk, wv, bv, wm, bm, w0, b0, w3, b3 = P
     B, C, N = x.shape
     M = src.shape[2]
@@ -73,15 +63,8 @@ def _prop_fwd(x, src, P, heads, eps, nx=None, nsrc=None, keep=True):
                    (src, f(wk), bk, 1, B * M, M, C, 2 * C, kv), dict(w2=f(wv), bias2=bv, wsplit=C))
     a = torch.empty((B, C, N), dtype=torch.float32, device=dev)
     lse = torch.empty((B, heads, N, 2), dtype=torch.float32, device=dev)
-    import ctypes
-    vptr = ctypes.c_void_p(kv.data_ptr() + 4 * C * M)
     masked = nx is not None or nsrc is not None
-    if masked:
-        call("pk_attention_fwd_varlen", ptr(q), ptr(kv), vptr, B, D, heads, N, M, 2 * C * M, 2 * C * M, ptr(nx),
-             ptr(nsrc), ptr(a), ptr(lse), _lib.stream(dev), work=("mfma", 2 * 2 * N * M * D * B * heads))
-    else:
-        call("pk_attention_fwd", ptr(q), ptr(kv), vptr, B, D, heads, N, M, 2 * C * M, 2 * C * M, ptr(a), ptr(lse),
-             _lib.stream(dev), work=("mfma", 2 * 2 * N * M * D * B * heads))
+    ops.attention_fwd_raw(q, kv[:, :C], kv[:, C:], B, D, heads, N, M, a, lse, nx, nsrc, ldkv=2 * C * M)
     h1n = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
     mean = torch.empty((B * 2 * C,), dtype=torch.float32, device=dev)
     invstd = torch.empty_like(mean)
@@ -98,12 +81,7 @@ def _prop_fwd(x, src, P, heads, eps, nx=None, nsrc=None, keep=True):
         ops.linear_ex(a, f(wm), bm, 1, B * N, N, C, C, y=hc[:, C:], ldy=2 * C * N)
         h1 = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
         ops.linear_ex(hc, f(w0), b0, 1, B * N, N, 2 * C, 2 * C, y=h1)
-        if masked:
-            call("pk_instnorm_relu_fwd_varlen", ptr(h1), B * 2 * C, N, float(eps), ptr(h1n), ptr(mean), ptr(invstd),
-                 2 * C, ptr(nx), _lib.stream(dev), work=("hbm", 8 * B * 2 * C * N))
-        else:
-            call("pk_instnorm_relu_fwd", ptr(h1), B * 2 * C, N, float(eps), ptr(h1n), ptr(mean), ptr(invstd),
-                 _lib.stream(dev), work=("hbm", 8 * B * 2 * C * N))
+        ops.instnorm_relu_fwd_raw(h1, B * 2 * C, N, eps, h1n, mean, invstd, 2 * C, nx, varlen=masked)
     out = torch.empty((B, C, N), dtype=torch.float32, device=dev)
     ops.linear_ex(h1n, f(w3), b3, 1, B * N, N, 2 * C, C, y=out, add=x, add_cols=C)
     return out, (x, src, q, kv, a, lse, hc, h1, h1n, mean, invstd)
@@ -120,48 +98,32 @@ def _prop_bwd(saved, P, heads, dout, dsrc_add=None, nx=None, nsrc=None):
     dev = x.device
     f = lambda w: w.view(w.shape[0], -1)  # noqa: E731
     dout = dout.contiguous()
-    masked = nx is not None or nsrc is not None  # (work= figures: padded shapes, as in _prop_fwd)
+    masked = nx is not None or nsrc is not None
     dh1 = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
     dhc = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
     da = torch.empty((B, C, N), dtype=torch.float32, device=dev)
     if _mlp_fused("bwd", C, N, masked):
         # mlp.3^T + the norm backward, then mlp.0^T + merge^T: two launches, dh1n never stored
         ops.attn_mlp_bwd_norm(dout, f(w3), h1, mean, invstd, dh1)
-        g_w3, g_b3 = _wgrad(h1n, dout, w3, b3)
+        g_w3, g_b3 = weight_grad(h1n, dout, w3, b3, True)
         ops.attn_mlp_bwd_in(dh1, f(w0), f(wm), dhc, da)
-        g_w0, g_b0 = _wgrad(hc, dh1, w0, b0)
+        g_w0, g_b0 = weight_grad(hc, dh1, w0, b0, True)
     else:
         # mlp.3 (its residual: dout flows to desc unchanged, added in Pq^T's epilogue below)
         dh1n = torch.empty((B, 2 * C, N), dtype=torch.float32, device=dev)
         ops.linear_ex(dout, f(w3), None, 1, B * N, N, C, 2 * C, y=dh1n, transw=True)
-        g_w3, g_b3 = _wgrad(h1n, dout, w3, b3)
-        if masked:
-            call("pk_instnorm_relu_bwd_varlen", ptr(h1), ptr(dh1n), ptr(mean), ptr(invstd), B * 2 * C, N, ptr(dh1),
-                 2 * C, ptr(nx), _lib.stream(dev), work=("hbm", 12 * B * 2 * C * N))
-        else:
-            call("pk_instnorm_relu_bwd", ptr(h1), ptr(dh1n), ptr(mean), ptr(invstd), B * 2 * C, N, ptr(dh1),
-                 _lib.stream(dev), work=("hbm", 12 * B * 2 * C * N))
+        g_w3, g_b3 = weight_grad(h1n, dout, w3, b3, True)
+        ops.instnorm_relu_bwd_raw(h1, dh1n, mean, invstd, B * 2 * C, N, dh1, 2 * C, nx, varlen=masked)
         ops.linear_ex(dh1, f(w0), None, 1, B * N, N, 2 * C, 2 * C, y=dhc, transw=True)
-        g_w0, g_b0 = _wgrad(hc, dh1, w0, b0)
+        g_w0, g_b0 = weight_grad(hc, dh1, w0, b0, True)
         # merge^T on the message half of the concatenation gradient, read in place
         ops.linear_ex(dhc[:, C:], f(wm), None, 1, B * N, N, C, C, y=da, transw=True, ldx=2 * C * N)
-    g_wm, g_bm = _wgrad(a, dhc[:, C:], wm, bm)
+    g_wm, g_bm = weight_grad(a, dhc[:, C:], wm, bm, True)
     # attention backward: dk / dv into one stacked buffer
     dq = torch.empty((B, C, N), dtype=torch.float32, device=dev)
     dkv = torch.empty((B, 2 * C, M), dtype=torch.float32, device=dev)
-    work = ops.attention_bwd_work(B, D, heads, N, M, dev)
-    import ctypes
-    off = 4 * C * M
-    if masked:
-        call("pk_attention_bwd_varlen", ptr(q), ptr(kv), ctypes.c_void_p(kv.data_ptr() + off), ptr(a), ptr(da),
-             ptr(lse), B, D, heads, N, M, 2 * C * M, 2 * C * M, ptr(nx), ptr(nsrc), ptr(work), ptr(dq), ptr(dkv),
-             ctypes.c_void_p(dkv.data_ptr() + off), 2 * C * M, 2 * C * M, _lib.stream(dev),
-             work=("mfma", 5 * 2 * N * M * D * B * heads))
-    else:
-        call("pk_attention_bwd", ptr(q), ptr(kv), ctypes.c_void_p(kv.data_ptr() + off), ptr(a), ptr(da), ptr(lse),
-             B, D, heads, N, M, 2 * C * M, 2 * C * M, ptr(work), ptr(dq), ptr(dkv),
-             ctypes.c_void_p(dkv.data_ptr() + off), 2 * C * M, 2 * C * M, _lib.stream(dev),
-             work=("mfma", 5 * 2 * N * M * D * B * heads))  # S, dP, dV, dK, dQ: each contraction once
+    ops.attention_bwd_raw(q, kv[:, :C], kv[:, C:], a, da, lse, B, D, heads, N, M, dq, dkv[:, :C], dkv[:, C:],
+                          nx, nsrc, ldkv=2 * C * M)
     # d desc = Pq^T dq + dout (residual) + dhc[:, :C] (concatenation) and d src = Pk^T dk + Pv^T dv
     # (+ the source's other gradient; the stacked weight's transpose, 64 -> 32): independent, one
     # launch (pk_linear_ex2)
@@ -173,9 +135,9 @@ def _prop_bwd(saved, P, heads, dout, dsrc_add=None, nx=None, nsrc=None):
                    dict(transw=True, add=dout, add_cols=C, add2=dhc[:, :C], lda2=2 * C * N),
                    (dkv, f(wk), None, 1, B * M, M, 2 * C, C, dsrc),
                    dict(transw=True, w2=f(wv), wsplit=C, add=dsrc_add, add_cols=C if dsrc_add is not None else 0))
-    g_wq, g_bq = _wgrad(x, dq, wq, bq)
-    g_wk, g_bk = _wgrad(src, dkv[:, :C], wk, bk)
-    g_wv, g_bv = _wgrad(src, dkv[:, C:], wv, bv)
+    g_wq, g_bq = weight_grad(x, dq, wq, bq, True)
+    g_wk, g_bk = weight_grad(src, dkv[:, :C], wk, bk, True)
+    g_wv, g_bv = weight_grad(src, dkv[:, C:], wv, bv, True)
     return dx, dsrc, [g_wq, g_bq, g_wk, g_bk, g_wv, g_bv, g_wm, g_bm, g_w0, g_b0, g_w3, g_b3]
 
 
@@ -252,8 +214,6 @@ def attn_prop_pair(layer, x0: torch.Tensor, x1: torch.Tensor, nx=None, nsrc=None
     nx / nsrc (masked mode): the real points of x0 / x1, int32 [B] on the device."""
     if not (_fusable(layer, x0, x1) and _fusable(layer, x1, x0)):
         return None
-    if nx is None and nsrc is None:
-        return _AttnPropPairFn.apply(x0, x1, *_params(layer), layer.attn.num_heads, float(layer.mlp[1].eps))
     B, dev = x0.shape[0], x0.device
     return _AttnPropPairFn.apply(x0, x1, *_params(layer), layer.attn.num_heads, float(layer.mlp[1].eps),
                                  ops._lens(nx, B, dev), ops._lens(nsrc, B, dev))
@@ -265,8 +225,6 @@ def attn_prop_residual(layer, x: torch.Tensor, src: torch.Tensor, nx=None, nsrc=
     nx / nsrc (masked mode): the real points of x / src, int32 [B] on the device."""
     if not _fusable(layer, x, src):
         return None
-    if nx is None and nsrc is None:
-        return _AttnPropFn.apply(x, src, *_params(layer), layer.attn.num_heads, float(layer.mlp[1].eps))
     B, dev = x.shape[0], x.device
     return _AttnPropFn.apply(x, src, *_params(layer), layer.attn.num_heads, float(layer.mlp[1].eps),
                              ops._lens(nx, B, dev), ops._lens(nsrc, B, dev))

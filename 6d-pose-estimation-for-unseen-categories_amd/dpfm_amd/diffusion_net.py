@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from . import ops
 from .layers import Linear
+from .wgrad import direct_grad, weight_grad
 
 # The whole configured DiffusionNet as one autograd node (_EncoderFn); False runs the per-module
 # path (the parity tests compare the two)
@@ -75,7 +76,7 @@ class _BlockMLPFn(torch.autograd.Function):
     """mlp(cat[x_in, x_diffuse]) + x_in for the configured MiniMLP (128 -> 64 -> 64 -> 64, ReLU
     between): one launch per direction (ops.mlp3_fwd / ops.mlp3_bwd: the activations stay in the
     wave between the layers, the ReLU masks on the saved h1 / h2 and the residual are epilogues),
-    and the weight gradients recorded for the grouped launch (layers.GroupedWgrad) or computed
+    and the weight gradients recorded for the grouped launch (wgrad.GroupedWgrad) or computed
     per layer."""
 
     @staticmethod
@@ -93,25 +94,16 @@ class _BlockMLPFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from . import layers
         x_in, x_diff, h1, h2, w1, w2, w3 = ctx.saved_tensors
-        P = ctx.params
+        p1, b1, p2, b2, p3, b3 = ctx.params
         dy = dy.contiguous()
-        grads = [None] * 6
-
-        def wgrad(x, d, k):  # layer k (0..2): weight P[2k], bias P[2k + 1]
-            if layers._side_owns(P[2 * k], P[2 * k + 1]):
-                layers._SIDE.launch(x, d, P[2 * k], P[2 * k + 1], channels_first=False)
-            else:
-                dw, grads[2 * k + 1] = ops.linear_wgrad(x, d, channels_first=False, want_bias=True)
-                grads[2 * k] = dw.view(P[2 * k].shape)
-
         d2, d1, dx_in, dx_diff = (torch.empty_like(dy) for _ in range(4))
         ops.mlp3_bwd(dy, h2, h1, w3, w2, w1, dy.numel() // 64, d2, d1, dx_in, dx_diff)
-        wgrad(h2, dy, 2)
-        wgrad(h1, d2, 1)
-        wgrad(torch.cat((x_in, x_diff), dim=-1), d1, 0)  # (the module path: not the training step's)
-        return (dx_in, dx_diff, *grads)
+        g3 = weight_grad(h2, dy, p3, b3, False)
+        g2 = weight_grad(h1, d2, p2, b2, False)
+        cat = torch.cat((x_in, x_diff), dim=-1)  # (the module path: not the training step's)
+        g1 = weight_grad(cat, d1, p1, b1, False)
+        return (dx_in, dx_diff, *g1, *g2, *g3)
 
 
 class SpatialGradientFeatures(nn.Module):
@@ -228,17 +220,6 @@ class DiffusionNetBlock(nn.Module):
         return self.mlp(torch.cat((x_in, x_diffuse), dim=-1)) + x_in
 
 
-def _wgrad(x, dy, weight, bias):
-    """Weight / bias gradients of a rows-layout layer: recorded for the grouped launch of the
-    training step (layers.GroupedWgrad) or computed now. Returns (dw, db) or (None, None)."""
-    from . import layers
-    if layers._side_owns(weight, bias):
-        layers._SIDE.launch(x, dy, weight, bias, channels_first=False)
-        return None, None
-    dw, db = ops.linear_wgrad(x, dy, channels_first=False, want_bias=bias is not None)
-    return dw.view(weight.shape), db
-
-
 class _EncoderFn(torch.autograd.Function):
     """The configured DiffusionNet (first_lin 3 -> 64, N_block blocks of spectral diffusion +
     MLP 128 -> 64 -> 64 -> 64 with ReLUs and the residual, last_lin 64 -> C_out) over rows
@@ -308,14 +289,13 @@ class _EncoderFn(torch.autograd.Function):
         dfeat = dfeat.contiguous()
         Cout = wl.shape[0]
         grads = [None] * len(params)
-        gw = _wgrad(Y, dfeat, wl, bl)
-        grads[-2], grads[-1] = gw
+        grads[-2], grads[-1] = weight_grad(Y, dfeat, wl, bl, False)
         dy = torch.empty((B, N, 64), dtype=torch.float32, device=dev)
         ops.linear_ex(dfeat, wl, None, 0, R, 0, Cout, 64, y=dy, transw=True)
         for i in reversed(range(nb)):
             t, w1, b1, w2, b2, w3, b3 = blocks[i]
             k = 2 + 7 * i
-            grads[k + 5], grads[k + 6] = _wgrad(h2s[i], dy, w3, b3)
+            grads[k + 5], grads[k + 6] = weight_grad(h2s[i], dy, w3, b3, False)
             d2 = torch.empty_like(dy)
             d1 = torch.empty_like(dy)
             dX = torch.empty_like(dy)
@@ -325,22 +305,21 @@ class _EncoderFn(torch.autograd.Function):
                 ops.mlp3_bwd(dy, h2s[i], h1s[i], w3, w2, w1, R, d2, d1, dX, dD)
             else:
                 ops.linear_ex(dy, w3, None, 0, R, 0, 64, 64, y=d2, transw=True, mask=h2s[i])
-            grads[k + 3], grads[k + 4] = _wgrad(h1s[i], d2, w2, b2)
+            grads[k + 3], grads[k + 4] = weight_grad(h1s[i], d2, w2, b2, False)
             if not chain:
                 ops.linear_ex(d2, w2, None, 0, R, 0, 64, 64, y=d1, transw=True, mask=h1s[i])
-            grads[k + 1], grads[k + 2] = _wgrad(cats[i], d1, w1, b1)
+            grads[k + 1], grads[k + 2] = weight_grad(cats[i], d1, w1, b1, False)
             if not chain:
                 # dcat = d1 W1: columns 0..63 (+ the residual's dy) -> dX, 64..127 -> dD
                 ops.linear_ex(d1, w1, None, 0, R, 0, 64, 128, y=dX, transw=True, y2=dD, split=64, add=dy, add_cols=64)
             # dL/dt straight into t's persistent .grad when the grouped weight gradient owns it (no
             # autograd accumulation launch)
-            from . import layers
-            gbuf = layers._SIDE.direct(t) if layers._SIDE is not None else None
+            gbuf = direct_grad(t)
             gt = gbuf if gbuf is not None else torch.empty((64,), dtype=torch.float32, device=dev)
             ops.spectral_raw(dD, 64, mass, evals, evecs, t, True, 1, dX, 64, saved=raws[i], gt=gt, accumulate=True)
             grads[k] = None if gbuf is not None else gt
             dy = dX
-        grads[0], grads[1] = _wgrad(fcat, dy, w0, b0)
+        grads[0], grads[1] = weight_grad(fcat, dy, w0, b0, False)
         dfcat = None
         if ctx.needs_input_grad[0]:  # the features are data in DPFM; kept for API completeness
             dfcat = torch.empty_like(fcat)

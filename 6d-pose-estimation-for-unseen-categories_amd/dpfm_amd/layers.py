@@ -17,8 +17,8 @@ import torch.nn.functional as F
 from typing import Optional
 
 from . import ops
+from .wgrad import GroupedWgrad, weight_grad  # noqa: F401  (GroupedWgrad: this module's public name for it)
 
-_SIDE = None  # the active GroupedWgrad (TrainStep's backward), or None
 FOLD_RELU = True  # fold a producer layer's ReLU backward into the consumer's input gradient
 # input gradients whose producer ReLU mask a consumer already applied: (dx storage pointer,
 # mask storage pointer) -> dx's version counter when the mask was applied. Keyed by storage, not
@@ -40,104 +40,17 @@ def _masked_put(dx, mask) -> None:
     _MASKED[(dx.data_ptr(), mask.data_ptr())] = (dx._version, dx)
 
 
+def reset_relu_fold() -> None:
+    """Drop the entries an earlier backward left behind (TrainStep, before each backward)."""
+    _MASKED.clear()
+
+
 def _masked_pop(dy, y) -> bool:
     """True when the consumer of `dy` already applied the ReLU mask `y` (and drops the entry)."""
     if not _MASKED:
         return False
     ent = _MASKED.pop((dy.data_ptr(), y.data_ptr()), None)
     return ent is not None and ent[0] == dy._version
-
-
-class GroupedWgrad:
-    """Weight gradients of all per-point layers of one backward in two launches.
-
-    Each layer's backward records (x, dy) instead of launching pk_linear_wgrad (two
-    launches per layer, 56 per training step, each too small to fill the chip) and returns
-    None for its weight / bias so autograd leaves their .grad alone. `end()` issues one
-    grouped pk_linear_wgrad_grouped on the same stream, writing into persistent .grad
-    buffers; a weight used twice in the forward (the refinement layer, modeling/dpfm.py:
-    100-104; first/last_lin on both shapes) accumulates in autograd's order. Everything
-    stays on one stream: a single-stream HIP graph replays without cross-queue
-    dependencies (a forked side stream measured slower on MI355X)."""
-
-    def __init__(self, params, bufs=None, direct_params=()):
-        """params: the per-point layers' weights / biases (gradients from the grouped launch);
-        direct_params: parameters whose gradient a kernel may write whole through direct() (the
-        diffusion times under the fused encoder) and that otherwise get autograd's ordinary
-        accumulation (the non-fused encoder path) — never zeroed by end()."""
-        self.params = [p for p in params]
-        self.direct_params = [p for p in direct_params]
-        self.direct_ids = {id(p) for p in self.direct_params}
-        self.caller_bufs = bufs is not None
-        # persistent .grad buffers (optionally the caller's, e.g. views of one flat buffer the
-        # caller zeroes before each backward)
-        self.bufs = {id(p): (bufs[id(p)] if bufs is not None else
-                             torch.zeros_like(p, memory_format=torch.contiguous_format))
-                     for p in self.params + self.direct_params}
-        self.seen = set()
-        self.calls = []
-
-    def begin(self):
-        global _SIDE
-        _MASKED.clear()
-        for p in self.params:
-            p.grad = self.bufs[id(p)]
-        for p in self.direct_params:
-            # autograd accumulates into .grad when no kernel writes it whole: start it from zero
-            # (a caller's flat buffer is already zeroed; an own buffer holds the last step's value)
-            if not self.caller_bufs:
-                self.bufs[id(p)].zero_()
-            p.grad = self.bufs[id(p)]
-        self.seen = set()
-        self.calls = []
-        _SIDE = self
-
-    def owns(self, p) -> bool:
-        return id(p) in self.bufs
-
-    def direct(self, p):
-        """p's persistent .grad buffer for a kernel that writes p's whole gradient itself (e.g. the
-        diffusion-time gradient of pk_spectral_diffusion's backward), on p's first use in this
-        backward; None otherwise (the caller then returns the gradient to autograd)."""
-        if id(p) not in self.bufs or id(p) in self.seen:
-            return None
-        self.seen.add(id(p))
-        return self.bufs[id(p)]
-
-    def launch(self, x, dy, weight, bias, channels_first: bool):
-        acc = id(weight) in self.seen
-        self.seen.add(id(weight))
-        if bias is not None:
-            self.seen.add(id(bias))
-        dw = self.bufs[id(weight)]
-        db = self.bufs[id(bias)] if bias is not None else None
-        self.calls.append((x, dy, channels_first, dw.view(dw.shape[0], -1), db, acc))
-
-    @staticmethod
-    def _groupable(c) -> bool:
-        x, dy, cf, dw, _, _ = c
-        O, I = dw.shape
-        return ((O + 31) // 32) * ((I + 31) // 32) <= 8
-
-    def end(self, run: bool = True):
-        global _SIDE
-        _SIDE = None
-        if run:
-            if all(self._groupable(c) for c in self.calls):
-                ops.linear_wgrad_grouped(self.calls)
-            else:  # a shape outside the grouped kernel's range: one launch pair per call, in order
-                for x, dy, cf, dw, db, acc in self.calls:
-                    ops.linear_wgrad(x, dy, channels_first=cf, want_bias=db is not None, dw=dw, db=db,
-                                     accumulate=acc)
-            for p in self.params:  # a layer the forward did not use gets a zero gradient
-                if id(p) not in self.seen:
-                    p.grad.zero_()
-            # (direct_params: written by direct(), or accumulated by autograd into the zeroed buffer)
-        self.calls = []
-
-
-def _side_owns(weight, bias) -> bool:
-    return _SIDE is not None and _SIDE.owns(weight) and (bias is None or _SIDE.owns(bias))
 
 
 class _PointwiseFn(torch.autograd.Function):
@@ -203,11 +116,7 @@ class _PointwiseFn(torch.autograd.Function):
             if ctx.in_relu:
                 _masked_put(dx, x)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            if _side_owns(ctx.param, ctx.bias):
-                _SIDE.launch(x, dy, ctx.param, ctx.bias, channels_first=cf)
-            else:
-                dw, db = ops.linear_wgrad(x, dy, channels_first=cf, want_bias=ctx.has_bias)
-                dw = dw.view(weight.shape)
+            dw, db = weight_grad(x, dy, ctx.param, ctx.bias, cf)
         return dx, dw, db, None, None, None, None
 
 
@@ -240,11 +149,7 @@ class _PointwiseResidualFn(torch.autograd.Function):
             if ctx.in_relu:
                 _masked_put(dx, x)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            if _side_owns(ctx.param, ctx.bias):
-                _SIDE.launch(x, dy, ctx.param, ctx.bias, channels_first=True)
-            else:
-                dw, db = ops.linear_wgrad(x, dy, channels_first=True, want_bias=ctx.has_bias)
-                dw = dw.view(weight.shape)
+            dw, db = weight_grad(x, dy, ctx.param, ctx.bias, True)
         return dx, dw, db, dy if ctx.needs_input_grad[3] else None, None
 
 
@@ -282,11 +187,7 @@ class _LinearPairCfFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = ops.linear_fwd(dyr, w2, None, channels_first=False, transw=True)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            if _side_owns(ctx.param, ctx.bias):
-                _SIDE.launch(feat, dyr, ctx.param, ctx.bias, channels_first=False)
-            else:
-                dw, db = ops.linear_wgrad(feat, dyr, channels_first=False, want_bias=ctx.has_bias)
-                dw = dw.view(weight.shape)
+            dw, db = weight_grad(feat, dyr, ctx.param, ctx.bias, False)
         return dx, dw, db, None
 
 

@@ -17,6 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from ..overlap_head import lastlin_overlap_head, overlap_head
 from ..layers import Conv1d, Linear, pointwise_residual
 from ..dpfm_utils import get_mask_batched
 
@@ -35,7 +36,7 @@ class InstanceNormReLU(nn.InstanceNorm1d):
 
 
 FUSED_ATTN_PROP = True  # AttentionalPropagation + residual as one fused node (attnprop.py)
-FUSED_OVERLAP_HEAD = True  # OverlapPredictorNet for both shapes as one fused node (ops.overlap_head)
+FUSED_OVERLAP_HEAD = True  # OverlapPredictorNet for both shapes as one fused node (overlap_head.overlap_head)
 
 
 def MLP(channels: list, do_bn=True):
@@ -179,8 +180,8 @@ class CrossAttentionRefinementNet(nn.Module):
             # last_lin + the overlap head as one node: the refined features' two consumers (the
             # overlap head here, the fmap head downstream) meet in one launch's epilogue
             l0, l2 = op.overlap_score_net[0], op.overlap_score_net[2]
-            y0, y1, sx, sy, rx, ry = ops.lastlin_overlap_head(desc0, desc1, ll.weight, ll.bias, l0.weight, l0.bias,
-                                                              l2.weight, l2.bias)
+            y0, y1, sx, sy, rx, ry = lastlin_overlap_head(desc0, desc1, ll.weight, ll.bias, l0.weight, l0.bias,
+                                                          l2.weight, l2.bias)
             ref_x, ref_y = y0.transpose(1, 2), y1.transpose(1, 2)
             if rx is not None:
                 ref_x._pk_nrows, ref_y._pk_nrows = rx, ry
@@ -219,10 +220,10 @@ class OverlapPredictorNet(nn.Module):
 
     def forward(self, overlap_feat_x, overlap_feat_y):
         if self._fusable(overlap_feat_x, overlap_feat_y):
-            # the whole head for both shapes in one launch per direction (ops.overlap_head); the
-            # rows copies of the normalized features go to the loss's NCE term as below
+            # the whole head for both shapes in one launch per direction (overlap_head.py); the rows
+            # copies of the normalized features go to the loss's NCE term as below
             l0, l2 = self.overlap_score_net[0], self.overlap_score_net[2]
-            sx, sy, rx, ry = ops.overlap_head(overlap_feat_x, overlap_feat_y, l0.weight, l0.bias, l2.weight, l2.bias)
+            sx, sy, rx, ry = overlap_head(overlap_feat_x, overlap_feat_y, l0.weight, l0.bias, l2.weight, l2.bias)
             if rx is not None:
                 overlap_feat_x._pk_nrows, overlap_feat_y._pk_nrows = rx, ry
             return sx.squeeze(0), sy.squeeze(0)  # [B, N] = the reference's [B, N, 1].squeeze(2).squeeze(0)

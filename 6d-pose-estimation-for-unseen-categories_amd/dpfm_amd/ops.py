@@ -197,7 +197,6 @@ def fps_npoint(off: torch.Tensor, fixed: int = 0, limit: int = 2000, seed: int =
 
 
 def ctypes_u64(v: int):
-    import ctypes
     return ctypes.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
 
 
@@ -347,7 +346,6 @@ def resolvent_mask(evals1: torch.Tensor, evals2: torch.Tensor, gamma: float = 0.
     if evals1.stride(1) != 1 or evals2.stride(1) != 1:
         evals1, evals2 = evals1.contiguous(), evals2.contiguous()
     D = torch.empty((B, K, K), dtype=torch.float32, device=evals1.device)
-    import ctypes
     call("pk_resolvent_mask", ctypes.c_void_p(evals1.data_ptr()), int(evals1.stride(0)),
          ctypes.c_void_p(evals2.data_ptr()), int(evals2.stride(0)), B, K, float(gamma), ptr(D),
          _lib.stream(evals1.device))
@@ -362,7 +360,6 @@ class _FmapHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, fx, fy, evecs_x, evecs_y, mass_x, mass_y, evals_x, evals_y, lambda_, gamma):
-        import ctypes
         B, N1, Cf = fx.shape
         N2 = fy.shape[1]
         dev = fx.device
@@ -389,7 +386,6 @@ class _FmapHeadFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, G):
-        import ctypes
         evecs_x, evecs_y, mass_x, mass_y, A, Bm, AAt, BAt, D = ctx.saved_tensors
         G = G.contiguous()
         B, K, _ = AAt.shape
@@ -429,35 +425,6 @@ def fmap_solve(AAt: torch.Tensor, BAt: torch.Tensor, D: torch.Tensor, lambda_: f
 # ------------------------------------------------------------------------------ H8 attention
 
 
-class _Attention(torch.autograd.Function):
-    """softmax(q^T k / sqrt(dim)) v per (crop, head), fused (pk_attention_fwd / _bwd)."""
-
-    @staticmethod
-    def forward(ctx, q, k, v):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        B, D, H, N = q.shape
-        M = k.shape[3]
-        out = torch.empty_like(q)
-        lse = torch.empty((B, H, N, 2), dtype=torch.float32, device=q.device)  # (row max, 1/sum)
-        call("pk_attention_fwd", ptr(q), ptr(k), ptr(v), B, D, H, N, M, 0, 0, ptr(out), ptr(lse),
-             _lib.stream(q.device), work=("mfma", 2 * 2 * N * M * D * B * H))  # S = Q K^T, O = P V
-        ctx.save_for_backward(q, k, v, out, lse)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v, out, lse = ctx.saved_tensors
-        dout = dout.contiguous()
-        B, D, H, N = q.shape
-        M = k.shape[3]
-        work = attention_bwd_work(B, D, H, N, M, q.device)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        call("pk_attention_bwd", ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), B, D, H, N, M, 0, 0,
-             ptr(work), ptr(dq), ptr(dk), ptr(dv), 0, 0, _lib.stream(q.device),
-             work=("mfma", 5 * 2 * N * M * D * B * H))  # S, dP, dV, dK, dQ: each contraction once
-        return dq, dk, dv
-
-
 def _lens(t, B: int, device) -> Optional[torch.Tensor]:
     """A per-crop length vector of masked mode as the kernels read it: int32 [B] on `device`,
     contiguous (None stays None: full length). A device tensor is never synced to the host."""
@@ -471,41 +438,65 @@ def _lens(t, B: int, device) -> Optional[torch.Tensor]:
     return t.contiguous()
 
 
-class _AttentionVarlen(torch.autograd.Function):
-    """_Attention over each crop's first qlen[b] queries and klen[b] keys (masked mode:
-    pk_attention_fwd_varlen / _bwd_varlen). Padded rows of out / dq / dk / dv are written as 0."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, qlen, klen):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        B, D, H, N = q.shape
-        M = k.shape[3]
-        out = torch.empty_like(q)
-        lse = torch.empty((B, H, N, 2), dtype=torch.float32, device=q.device)
-        # work: the padded shapes (an upper bound of what the lengths leave; they live on the device)
-        call("pk_attention_fwd_varlen", ptr(q), ptr(k), ptr(v), B, D, H, N, M, 0, 0, ptr(qlen), ptr(klen), ptr(out),
-             ptr(lse), _lib.stream(q.device), work=("mfma", 2 * 2 * N * M * D * B * H))
-        ctx.save_for_backward(q, k, v, out, lse, qlen, klen)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v, out, lse, qlen, klen = ctx.saved_tensors
-        dout = dout.contiguous()
-        B, D, H, N = q.shape
-        M = k.shape[3]
-        work = attention_bwd_work(B, D, H, N, M, q.device)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        call("pk_attention_bwd_varlen", ptr(q), ptr(k), ptr(v), ptr(out), ptr(dout), ptr(lse), B, D, H, N, M, 0, 0,
-             ptr(qlen), ptr(klen), ptr(work), ptr(dq), ptr(dk), ptr(dv), 0, 0, _lib.stream(q.device),
-             work=("mfma", 5 * 2 * N * M * D * B * H))  # (padded shapes, as above)
-        return dq, dk, dv, None, None
-
-
 def attention_bwd_work(B: int, D: int, H: int, N: int, M: int, device) -> Optional[torch.Tensor]:
     """Scratch of pk_attention_bwd (the dQ partials of key blocks 1 ..; None when one block covers M)."""
     nbytes = int(_lib.lib().pk_attention_bwd_work_size(B, D, H, N, M))
     return torch.empty((nbytes // 4,), dtype=torch.float32, device=device) if nbytes > 0 else None
+
+
+def attention_fwd_raw(q, k, v, B: int, D: int, H: int, N: int, M: int, out, lse, qlen=None, klen=None,
+                      ldkv: int = 0) -> None:
+    """pk_attention_fwd on caller-owned buffers, or pk_attention_fwd_varlen when either length is
+    given (masked mode). q, out: B crops of [D, H, N], contiguous; k, v: B crops of [D, H, M] at
+    batch stride ldkv elements (0: contiguous; the two halves of one stacked buffer otherwise);
+    lse f32 [B, H, N, 2] (row max, 1 / sum). The `work=` figure is the padded shapes' in masked
+    mode too (an upper bound of what the lengths leave: they live on the device)."""
+    args = (ptr(q), ctypes_ptr(k), ctypes_ptr(v), B, D, H, N, M, ldkv, ldkv)
+    tail = (ptr(out), ptr(lse), _lib.stream(q.device))
+    work = ("mfma", 2 * 2 * N * M * D * B * H)  # S = Q K^T, O = P V
+    if qlen is None and klen is None:
+        call("pk_attention_fwd", *args, *tail, work=work)
+    else:
+        call("pk_attention_fwd_varlen", *args, ptr(qlen), ptr(klen), *tail, work=work)
+
+
+def attention_bwd_raw(q, k, v, out, dout, lse, B: int, D: int, H: int, N: int, M: int, dq, dk, dv, qlen=None,
+                      klen=None, ldkv: int = 0) -> None:
+    """pk_attention_bwd (or _bwd_varlen, as attention_fwd_raw) on caller-owned buffers: dk, dv are
+    laid out as k, v (batch stride ldkv). Padded rows of dq / dk / dv are written as 0."""
+    scratch = attention_bwd_work(B, D, H, N, M, q.device)
+    args = (ptr(q), ctypes_ptr(k), ctypes_ptr(v), ptr(out), ptr(dout), ptr(lse), B, D, H, N, M, ldkv, ldkv)
+    tail = (ptr(scratch), ptr(dq), ctypes_ptr(dk), ctypes_ptr(dv), ldkv, ldkv, _lib.stream(q.device))
+    work = ("mfma", 5 * 2 * N * M * D * B * H)  # S, dP, dV, dK, dQ: each contraction once
+    if qlen is None and klen is None:
+        call("pk_attention_bwd", *args, *tail, work=work)
+    else:
+        call("pk_attention_bwd_varlen", *args, ptr(qlen), ptr(klen), *tail, work=work)
+
+
+class _Attention(torch.autograd.Function):
+    """softmax(q^T k / sqrt(dim)) v per (crop, head), fused (pk_attention_fwd / _bwd); with qlen /
+    klen (masked mode) over each crop's first qlen[b] queries and klen[b] keys (the _varlen entry
+    points): padded rows of out / dq / dk / dv are written as 0."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, qlen=None, klen=None):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        B, D, H, N = q.shape
+        out = torch.empty_like(q)
+        lse = torch.empty((B, H, N, 2), dtype=torch.float32, device=q.device)
+        attention_fwd_raw(q, k, v, B, D, H, N, k.shape[3], out, lse, qlen, klen)
+        ctx.lens = (qlen, klen)  # (not differentiable, never outputs: plain attributes)
+        ctx.save_for_backward(q, k, v, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        B, D, H, N = q.shape
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        attention_bwd_raw(q, k, v, out, dout.contiguous(), lse, B, D, H, N, k.shape[3], dq, dk, dv, *ctx.lens)
+        return dq, dk, dv, None, None
 
 
 def attention(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, qlen=None, klen=None) -> torch.Tensor:
@@ -518,10 +509,8 @@ def attention(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, qlen=
         raise _lib.PoseKernError("attention kernel is built for dim = 16 (gnn_dim 32, 2 heads)")
     if query.dtype != torch.float32:
         raise _lib.PoseKernError("attention kernel computes in fp32")
-    if qlen is None and klen is None:
-        return _Attention.apply(query, key, value)
     B = query.shape[0]
-    return _AttentionVarlen.apply(query, key, value, _lens(qlen, B, query.device), _lens(klen, B, query.device))
+    return _Attention.apply(query, key, value, _lens(qlen, B, query.device), _lens(klen, B, query.device))
 
 
 # ------------------------------------------------------------------------------ per-point layers
@@ -608,7 +597,6 @@ def clip_rmsprop(params, grads, square_avg, steps, max_norm: float, lr: float, a
     """clip_grad_norm_(max_norm) + RMSprop step (no momentum / centering / weight decay) over
     lists of f32 device tensors, in two launches (pk_clip_rmsprop). Updates params, grads
     (clipped), square_avg and steps in place."""
-    import ctypes
     n = len(params)
     if not (len(grads) == len(square_avg) == n and (steps is None or len(steps) == n)):
         raise _lib.PoseKernError("clip_rmsprop: list lengths differ")
@@ -625,15 +613,45 @@ def clip_rmsprop(params, grads, square_avg, steps, max_norm: float, lr: float, a
          ptr(norm_out), _lib.stream(dev), work=None)
 
 
+def instnorm_relu_fwd_raw(x, rows: int, N: int, eps: float, y, mean, invstd, C: int, lens=None,
+                          varlen: bool = False) -> None:
+    """pk_instnorm_relu_fwd on caller-owned buffers: x, y `rows` = B * C rows of N, mean / invstd
+    f32 [rows]. lens (masked mode; int32 [B], row r belongs to crop r / C): the _varlen entry
+    point, which `varlen` can also ask for without lengths (a masked node whose own side is full).
+    The `work=` figure is the padded shape's either way (an upper bound in masked mode)."""
+    work = ("hbm", 8 * rows * N)
+    if lens is not None or varlen:
+        call("pk_instnorm_relu_fwd_varlen", ptr(x), rows, N, float(eps), ptr(y), ptr(mean), ptr(invstd), C,
+             ptr(lens), _lib.stream(x.device), work=work)
+    else:
+        call("pk_instnorm_relu_fwd", ptr(x), rows, N, float(eps), ptr(y), ptr(mean), ptr(invstd),
+             _lib.stream(x.device), work=work)
+
+
+def instnorm_relu_bwd_raw(x, dy, mean, invstd, rows: int, N: int, dx, C: int, lens=None,
+                          varlen: bool = False) -> None:
+    """pk_instnorm_relu_bwd (or _bwd_varlen), arguments as instnorm_relu_fwd_raw's."""
+    work = ("hbm", 12 * rows * N)
+    if lens is not None or varlen:
+        call("pk_instnorm_relu_bwd_varlen", ptr(x), ptr(dy), ptr(mean), ptr(invstd), rows, N, ptr(dx), C, ptr(lens),
+             _lib.stream(x.device), work=work)
+    else:
+        call("pk_instnorm_relu_bwd", ptr(x), ptr(dy), ptr(mean), ptr(invstd), rows, N, ptr(dx),
+             _lib.stream(x.device), work=work)
+
+
 class _InstNormReLU(torch.autograd.Function):
+    """relu(InstanceNorm(x)); with lens (masked mode) the statistics are over each crop's first
+    lens[b] points."""
+
     @staticmethod
-    def forward(ctx, x, eps):
+    def forward(ctx, x, eps, lens=None):
         B, C, N = x.shape
         y = torch.empty_like(x)
         mean = torch.empty((B * C,), dtype=torch.float32, device=x.device)
         invstd = torch.empty_like(mean)
-        call("pk_instnorm_relu_fwd", ptr(x), B * C, N, float(eps), ptr(y), ptr(mean), ptr(invstd),
-             _lib.stream(x.device), work=("hbm", 8 * B * C * N))
+        instnorm_relu_fwd_raw(x, B * C, N, eps, y, mean, invstd, C, lens)
+        ctx.lens = lens  # (not differentiable, never an output: a plain attribute)
         ctx.save_for_backward(x, mean, invstd)
         return y
 
@@ -641,35 +659,8 @@ class _InstNormReLU(torch.autograd.Function):
     def backward(ctx, dy):
         x, mean, invstd = ctx.saved_tensors
         B, C, N = x.shape
-        dy = dy.contiguous()
         dx = torch.empty_like(x)
-        call("pk_instnorm_relu_bwd", ptr(x), ptr(dy), ptr(mean), ptr(invstd), B * C, N, ptr(dx),
-             _lib.stream(x.device), work=("hbm", 12 * B * C * N))
-        return dx, None
-
-
-class _InstNormReLUVarlen(torch.autograd.Function):
-    """_InstNormReLU with the statistics over each crop's first lens[b] points (masked mode)."""
-
-    @staticmethod
-    def forward(ctx, x, eps, lens):
-        B, C, N = x.shape
-        y = torch.empty_like(x)
-        mean = torch.empty((B * C,), dtype=torch.float32, device=x.device)
-        invstd = torch.empty_like(mean)
-        call("pk_instnorm_relu_fwd_varlen", ptr(x), B * C, N, float(eps), ptr(y), ptr(mean), ptr(invstd), C,
-             ptr(lens), _lib.stream(x.device), work=("hbm", 8 * B * C * N))  # (padded shape: an upper bound)
-        ctx.save_for_backward(x, mean, invstd, lens)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, mean, invstd, lens = ctx.saved_tensors
-        B, C, N = x.shape
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        call("pk_instnorm_relu_bwd_varlen", ptr(x), ptr(dy), ptr(mean), ptr(invstd), B * C, N, ptr(dx), C, ptr(lens),
-             _lib.stream(x.device), work=("hbm", 12 * B * C * N))
+        instnorm_relu_bwd_raw(x, dy.contiguous(), mean, invstd, B * C, N, dx, C, ctx.lens)
         return dx, None, None
 
 
@@ -680,9 +671,7 @@ def instnorm_relu(x: torch.Tensor, eps: float = 1e-5, lens=None) -> torch.Tensor
     them."""
     if x.dim() != 3 or x.dtype != torch.float32:
         raise _lib.PoseKernError("instnorm_relu takes f32 [B, C, N]")
-    if lens is None:
-        return _InstNormReLU.apply(x.contiguous(), eps)
-    return _InstNormReLUVarlen.apply(x.contiguous(), eps, _lens(lens, x.shape[0], x.device))
+    return _InstNormReLU.apply(x.contiguous(), eps, _lens(lens, x.shape[0], x.device))
 
 
 def _wbce_call(p12, t12, p21, t21, n1, n2, loss, g12, g21) -> None:
@@ -723,8 +712,6 @@ def weighted_bce_pair(p12: torch.Tensor, p21: torch.Tensor, t12: torch.Tensor, t
     def mask(t):
         return (t if t.dtype == torch.int8 else (t >= 0.5).to(torch.int8)).contiguous()
     want = torch.is_grad_enabled() and (p12.requires_grad or p21.requires_grad)
-    if n1 is None and n2 is None:
-        return _WBCE.apply(p12.contiguous(), p21.contiguous(), mask(t12), mask(t21), want)
     B, dev = p12.shape[0], p12.device
     return _WBCE.apply(p12.contiguous(), p21.contiguous(), mask(t12), mask(t21), want, _lens(n1, B, dev),
                        _lens(n2, B, dev))
@@ -732,7 +719,6 @@ def weighted_bce_pair(p12: torch.Tensor, p21: torch.Tensor, t12: torch.Tensor, t
 
 def _l2_layout(x: torch.Tensor):
     """(tensor, strides) with unit stride on the channel or the point dim (copy otherwise)."""
-    import ctypes
     if x.stride(-1) != 1 and x.stride(1) != 1:
         x = x.contiguous()
     return x, (ctypes.c_int64 * 3)(*x.stride())
@@ -765,7 +751,6 @@ class _L2Normalize(torch.autograd.Function):
 
 def ctypes_ptr(t: torch.Tensor):
     """Device pointer of a (possibly non-contiguous, strides passed separately) tensor."""
-    import ctypes
     if not t.is_cuda:
         raise _lib.PoseKernError("posekern ops take HIP device tensors only (no CPU fallback)")
     return ctypes.c_void_p(t.data_ptr())
@@ -817,176 +802,6 @@ def l2_normalize(x: torch.Tensor) -> torch.Tensor:
         raise _lib.PoseKernError("l2_normalize takes f32 [B, N, C]")
     x, _ = _l2_layout(x)
     return _L2Normalize.apply(x)
-
-
-def _ovh_args(fx, fy, w0, b0, w1, b1):
-    import ctypes
-    a = _lib.OverlapHeadArgs()
-    for s, f in enumerate((fx, fy)):
-        a.x[s] = f.data_ptr()
-        for j in range(3):
-            a.strides[s][j] = f.stride(j)
-        a.N[s] = f.shape[1]
-    a.B = fx.shape[0]
-    a.w0, a.b0, a.w1, a.b1 = w0.data_ptr(), b0.data_ptr(), w1.data_ptr(), b1.data_ptr()
-    return a, ctypes
-
-
-def _ovh_forward(fx, fy, w0, b0, w1, b1, want: bool):
-    """pk_overlap_head_fwd on both shapes: ((s_x, s_y, nrows_x, nrows_y), the saved tensors)."""
-    B = fx.shape[0]
-    dev = fx.device
-    a, ctypes = _ovh_args(fx, fy, w0, b0, w1, b1)
-    outs = []
-    for s, f in enumerate((fx, fy)):
-        N = f.shape[1]
-        n = torch.empty_strided(f.shape, f.stride(), dtype=torch.float32, device=dev)
-        nrm = torch.empty((B * N,), dtype=torch.float32, device=dev)
-        nrows = torch.empty((B, N, 32), dtype=torch.float32, device=dev) if want else None
-        h = torch.empty((B, N, 32), dtype=torch.float32, device=dev) if want else None
-        sc = torch.empty((B, N), dtype=torch.float32, device=dev)
-        a.n[s], a.nrm[s] = n.data_ptr(), nrm.data_ptr()
-        a.nrows[s] = nrows.data_ptr() if nrows is not None else None
-        a.h[s] = h.data_ptr() if h is not None else None
-        a.s[s] = sc.data_ptr()
-        outs.append((n, nrm, nrows, h, sc))
-    call("pk_overlap_head_fwd", ctypes.addressof(a), _lib.stream(dev),
-         work=("hbm", 4 * B * (fx.shape[1] + fy.shape[1]) * (32 + 32 + (64 if want else 0) + 2)))
-    (nx, nrx, rx, hx, sx), (ny, nry, ry, hy, sy) = outs
-    return (sx, sy, rx, ry), (nx, nrx, rx, hx, sx, ny, nry, ry, hy, sy)
-
-
-def _ovh_backward(saved, params, dsx, dsy, drx, dry, dadd=(None, None)):
-    """pk_overlap_head_bwd on both shapes: (d f_x, d f_y (+ dadd, another consumer's gradient of
-    the features, added in the launch), the four weight gradients (None where the grouped launch
-    takes them))."""
-    from . import layers
-    nx, nrx, rx, hx, sx, ny, nry, ry, hy, sy = saved
-    w0, b0, w1, b1 = params
-    dev = nx.device
-    a, ctypes = _ovh_args(nx, ny, w0, b0, w1, b1)
-    B = nx.shape[0]
-    res = []
-    for s, (n, nrm, rows, h, sc, ds, dr, da) in enumerate(((nx, nrx, rx, hx, sx, dsx, drx, dadd[0]),
-                                                           (ny, nry, ry, hy, sy, dsy, dry, dadd[1]))):
-        N = n.shape[1]
-        ds = torch.zeros((B, N), dtype=torch.float32, device=dev) if ds is None else ds.contiguous()
-        dr = dr.contiguous() if dr is not None else None
-        g = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
-        dh = torch.empty((B, N, 32), dtype=torch.float32, device=dev)
-        dx = torch.empty_strided(n.shape, n.stride(), dtype=torch.float32, device=dev)
-        if da is not None and da.stride() != n.stride():
-            da = torch.empty_strided(n.shape, n.stride(), dtype=torch.float32, device=dev).copy_(da)
-        a.n[s], a.nrm[s], a.h[s], a.s[s] = n.data_ptr(), nrm.data_ptr(), h.data_ptr(), sc.data_ptr()
-        a.ds[s], a.dnr[s] = ds.data_ptr(), (dr.data_ptr() if dr is not None else None)
-        a.g[s], a.dh[s], a.dx[s] = g.data_ptr(), dh.data_ptr(), dx.data_ptr()
-        a.dadd[s] = da.data_ptr() if da is not None else None
-        res.append((rows, h, g, dh, dx, ds, dr, da))
-    call("pk_overlap_head_bwd", ctypes.addressof(a), _lib.stream(dev),
-         work=("hbm", 4 * B * (nx.shape[1] + ny.shape[1]) * (32 * 5 + 4) +
-               sum(4 * d.numel() for d in dadd if d is not None)))
-    gw0 = gb0 = gw1 = gb1 = None
-    side0 = layers._side_owns(w0, b0)
-    side1 = layers._side_owns(w1, b1)
-    for rows, h, g, dh, _, _, _, _ in res:
-        if side1:
-            layers._SIDE.launch(h, g, w1, b1, channels_first=False)
-        else:
-            dw, db = linear_wgrad(h, g, channels_first=False, want_bias=True)
-            gw1 = dw.view(w1.shape) if gw1 is None else gw1 + dw.view(w1.shape)
-            gb1 = db if gb1 is None else gb1 + db
-        if side0:
-            layers._SIDE.launch(rows, dh, w0, b0, channels_first=False)
-        else:
-            dw, db = linear_wgrad(rows, dh, channels_first=False, want_bias=True)
-            gw0 = dw.view(w0.shape) if gw0 is None else gw0 + dw.view(w0.shape)
-            gb0 = db if gb0 is None else gb0 + db
-    return res[0][4], res[1][4], gw0, gb0, gw1, gb1
-
-
-class _OverlapHeadFn(torch.autograd.Function):
-    """OverlapPredictorNet (modeling/dpfm.py:125-145) for both shapes as one autograd node:
-    F.normalize -> Linear(32, 32) + ReLU -> Linear(32, 1) + Sigmoid in one launch per direction
-    (pk_overlap_head_fwd / _bwd, bit-identical to the per-layer path). Outputs the two score maps
-    and the rows copies of the normalized features (the NCE term's input, utils/loss.py:23-24);
-    the weight gradients go to the grouped launch (layers.GroupedWgrad) or are computed here."""
-
-    @staticmethod
-    def forward(ctx, fx, fy, w0, b0, w1, b1):
-        outs, saved = _ovh_forward(fx, fy, w0, b0, w1, b1, any(ctx.needs_input_grad))
-        ctx.params = (w0, b0, w1, b1)
-        ctx.save_for_backward(*saved)
-        return outs
-
-    @staticmethod
-    def backward(ctx, dsx, dsy, drx, dry):
-        return _ovh_backward(ctx.saved_tensors, ctx.params, dsx, dsy, drx, dry)
-
-
-class _LastLinOverlapFn(torch.autograd.Function):
-    """The refinement's last_lin on both shapes (modeling/dpfm.py:111-112, desc.transpose(1, 2)
-    read in place: channels-first in and out) and the overlap head on its outputs (:125-145) as
-    one node, so the two consumers of the refined features — the overlap head and the fmap head
-    (models/dpfm.py:80-90) — meet inside it: the fmap head's gradient enters
-    pk_overlap_head_bwd's dadd and the features' total gradient leaves that launch (no autograd
-    accumulation kernel), then last_lin's input gradient and grouped weight gradient."""
-
-    @staticmethod
-    def forward(ctx, d0, d1, wl, bl, w0, b0, w1, b1):
-        w2 = wl.view(wl.shape[0], -1)
-        Co, Ci = w2.shape
-        ys = [torch.empty((d.shape[0], Co, d.shape[2]), dtype=torch.float32, device=d.device) for d in (d0, d1)]
-        linear_ex2(*[a for d, y in zip((d0, d1), ys)
-                     for a in ((d, w2, bl, 1, d.shape[0] * d.shape[2], d.shape[2], Ci, Co, y), {})])
-        fx, fy = ys[0].transpose(1, 2), ys[1].transpose(1, 2)
-        want = any(ctx.needs_input_grad)
-        (sx, sy, rx, ry), saved = _ovh_forward(fx, fy, w0, b0, w1, b1, want)
-        ctx.params = (w0, b0, w1, b1)
-        ctx.lin = (wl, bl)
-        ctx.save_for_backward(d0, d1, wl, *saved)
-        return ys[0], ys[1], sx, sy, rx, ry
-
-    @staticmethod
-    def backward(ctx, gy0, gy1, dsx, dsy, drx, dry):
-        from . import layers
-        sv = ctx.saved_tensors
-        d0, d1, wl = sv[:3]
-        wl_p, bl = ctx.lin
-        w2 = wl.view(wl.shape[0], -1)
-        Co, Ci = w2.shape
-        dadd = tuple(None if g is None else g.transpose(1, 2) for g in (gy0, gy1))
-        dfx, dfy, gw0, gb0, gw1, gb1 = _ovh_backward(sv[3:], ctx.params, dsx, dsy, drx, dry, dadd=dadd)
-        dd, gwl, gbl = [torch.empty_like(d0), torch.empty_like(d1)], None, None
-        dys = [df.transpose(1, 2) for df in (dfx, dfy)]  # [B, Co, N] contiguous (y's storage)
-        linear_ex2(*[a for d, dy, o in zip((d0, d1), dys, dd)
-                     for a in ((dy, w2, None, 1, d.shape[0] * d.shape[2], d.shape[2], Co, Ci, o), dict(transw=True))])
-        # weight gradients: shape 1 first, the order autograd ran the two last_lin calls' backward in
-        for s, (d, dy) in reversed(list(enumerate(zip((d0, d1), dys)))):
-            if layers._side_owns(wl_p, bl):
-                layers._SIDE.launch(d, dy, wl_p, bl, channels_first=True)
-            else:
-                dw, db = linear_wgrad(d, dy, channels_first=True, want_bias=bl is not None)
-                gwl = dw.view(wl.shape) if gwl is None else gwl + dw.view(wl.shape)
-                gbl = db if gbl is None else (gbl + db if db is not None else gbl)
-        return dd[0], dd[1], gwl, gbl, gw0, gb0, gw1, gb1
-
-
-def lastlin_overlap_head(d0: torch.Tensor, d1: torch.Tensor, wl, bl, w0, b0, w1, b1):
-    """(y0, y1 [B, 32, N] channels-first last_lin outputs, s_x, s_y, nrows_x, nrows_y): the
-    refinement's last_lin + overlap head node (_LastLinOverlapFn)."""
-    return _LastLinOverlapFn.apply(d0, d1, wl, bl, w0.contiguous(), b0.contiguous(), w1.contiguous(), b1.contiguous())
-
-
-def overlap_head(fx: torch.Tensor, fy: torch.Tensor, w0, b0, w1, b1):
-    """(s_x [B, N1], s_y [B, N2], nrows_x, nrows_y) of OverlapPredictorNet's score net applied to
-    F.normalize(f, dim=-1) of both shapes, f32 [B, N, 32] in rows or channels-first storage."""
-    if (fx.dim() != 3 or fy.dim() != 3 or fx.shape[-1] != 32 or fy.shape[-1] != 32 or fx.shape[0] != fy.shape[0]
-            or fx.dtype != torch.float32 or fy.dtype != torch.float32):
-        raise _lib.PoseKernError("overlap_head takes f32 [B, N, 32] features of both shapes")
-    fx, _ = _l2_layout(fx)
-    fy, _ = _l2_layout(fy)
-    w0, b0, w1, b1 = (t.contiguous() for t in (w0, b0, w1, b1))
-    return _OverlapHeadFn.apply(fx, fy, w0, b0, w1, b1)
 
 
 _MLP3_WEIGHT_BYTES = 4 * (64 * 128 + 2 * 64 * 64)
@@ -1128,7 +943,6 @@ def linear_ex(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], la
     """pk_linear_ex: a per-point layer writing into caller-placed (strided) outputs with a
     residual / accumulation epilogue. x, y, y2, add are the first elements of their (possibly
     strided) operands; strides as in include/posekern.h (0 = contiguous)."""
-    import ctypes
     a, keep, byts, flops = _linear_args(x, w, bias, layout, R, N, Cin, Cout, y, **kw)
     call("pk_linear_ex", ctypes.addressof(a), _lib.stream(x.device), work=("hbm", byts, flops))
 
@@ -1136,7 +950,6 @@ def linear_ex(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], la
 def linear_ex2(args0: tuple, kw0: dict, args1: tuple, kw1: dict) -> None:
     """pk_linear_ex2: two independent linear_ex calls (positional args, keyword args each), one
     launch when both are channels-first 32/64-channel layers."""
-    import ctypes
     a0, k0, b0, f0 = _linear_args(*args0, **kw0)
     a1, k1, b1, f1 = _linear_args(*args1, **kw1)
     call("pk_linear_ex2", ctypes.addressof(a0), ctypes.addressof(a1), _lib.stream(args0[0].device),
@@ -1216,7 +1029,6 @@ class _NCELoss(torch.autograd.Function):
         N2 = f2.shape[1]
         S = rows.shape[1]
         dev = f1.device
-        import ctypes
         f1c, f2c = f1.detach(), f2.detach()
         if f1c.stride(-1) != 1 and f1c.stride(1) != 1:  # neither rows nor channels-first storage
             f1c = f1c.contiguous()
@@ -1270,7 +1082,6 @@ def affine_cat(a: torch.Tensor, b: torch.Tensor, sub: float, div: float) -> torc
 def _nce_raw(f1, f2, pairs, rows, valid, nce_t, want, prenorm=False):
     """pk_nce_loss: (loss [B], g1, g2) with g the gradients of each crop's loss (None unless
     want); prenorm: f1 / f2 already normalized, g with respect to them."""
-    import ctypes
     B, N1, C = f1.shape
     N2 = f2.shape[1]
     S = rows.shape[1]
@@ -1322,7 +1133,6 @@ class _DPFMLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gl, _glogs):
-        import ctypes
         saved = ctx.saved_tensors
         if gl is None:  # (not materialised: nothing flows into the loss)
             return (None,) * 16
@@ -1609,7 +1419,6 @@ def teaser_solve_host(src: np.ndarray, dst: np.ndarray, off: np.ndarray, nmax: i
     """pk_teaser_solve on host arrays (max clique / GNC-TLS / adaptive voting are native host
     code): (T f64 [B,4,4], clique int32 [B, nmax], clique_size int32 [B], info int32 [B, 4]).
     With `scale` (f64 [B]) pk_teaser_solve_scaled: adj / deg are the scaled graph."""
-    import ctypes
     B = off.shape[0] - 1
     c = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
     src = np.ascontiguousarray(src, dtype=np.float64)

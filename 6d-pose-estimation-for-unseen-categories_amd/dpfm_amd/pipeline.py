@@ -23,7 +23,8 @@ from . import _lib, ops
 from .dataset.object import CropFormation, Crops, FrameBatch
 from .dataset.synthetic import cad_points, lbo_operators, make_frame
 from .models.dpfm import DPFMNet
-from .layers import Conv1d, GroupedWgrad, Linear
+from .layers import Conv1d, Linear, reset_relu_fold
+from .wgrad import GroupedWgrad
 from .diffusion_net import LearnedTimeDiffusion
 from .utils.loss import DPFMLoss
 
@@ -269,7 +270,7 @@ class TrainStep:
         # clip + RMSprop in one HIP launch on HIP devices (torch's optimizer keeps the state)
         self.fused_opt = fused_opt and dev.type == "cuda" and len(self.params) <= 96
         # grouped=True (HIP devices): the per-point layers' weight gradients are recorded during
-        # backward and computed in one grouped launch pair at its end (layers.GroupedWgrad).
+        # backward and computed in one grouped launch pair at its end (wgrad.GroupedWgrad).
         # The step stays on one stream: forking C_gt / the IR onto an auxiliary stream inside
         # the captured graph replayed ~1 ms/step slower on MI355X.
         self.side = None
@@ -380,6 +381,7 @@ class TrainStep:
             for p, v in zip(self.params, self.gviews):
                 p.grad = v
         if self.side is not None:
+            reset_relu_fold()
             self.side.begin()
         ok = False
         if getattr(self, "_seed_grad", None) is None or self._seed_grad.device != loss.device:

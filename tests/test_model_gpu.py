@@ -620,7 +620,7 @@ def test_fused_encoder_matches_module_path(device, B, N, monkeypatch):
 @pytest.mark.parametrize("cf,N1,N2", [(True, 1024, 1024), (True, 300, 203), (False, 257, 130)])
 def test_fused_overlap_head_matches_layer_path(device, cf, N1, N2, monkeypatch):
     """OverlapPredictorNet (modeling/dpfm.py:125-145) for both shapes in one launch per direction
-    (ops.overlap_head) against the per-layer path (l2 normalize, 32 -> 32 MFMA layer, thin
+    (overlap_head.overlap_head) against the per-layer path (l2 normalize, 32 -> 32 MFMA layer, thin
     32 -> 1 sigmoid layer) on the same weights and inputs, channels-first and rows storage, ragged
     N: scores, the NCE rows copies and the feature gradients (with an NCE-like rows gradient
     added) bit-identical — same operations in the same order; weight gradients within 1e-5 of

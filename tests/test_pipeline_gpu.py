@@ -62,7 +62,7 @@ def test_train_and_infer_steps(device):
 
 
 def test_grouped_wgrad_step_matches_serial(device):
-    """TrainStep's grouped weight gradients (layers.GroupedWgrad: every per-point layer's
+    """TrainStep's grouped weight gradients (wgrad.GroupedWgrad: every per-point layer's
     dW / db recorded during backward, computed in one pk_linear_wgrad_grouped launch pair,
     shared layers accumulating). The recorded (x, dy) of every call are checked against an
     fp64 recomputation within the fp32 summation bound 1e-5 * sum_r |dy||x|; every layer
