@@ -39,63 +39,7 @@ __device__ __forceinline__ bool within(double ax, double ay, double az, double b
   return s <= thr2;
 }
 
-// grid: (ceil(n2max / 1024), ceil(n1max / 64), B); block 256 = 4 waves.
-// A lane owns 16 consecutive columns (their pc coords stay in registers) and walks
-// 16 rows; each row produces one 16-byte store.
-__global__ __launch_bounds__(kBqThreads) void bq_mask_kernel(
-    const double* __restrict__ cad, const int64_t* __restrict__ cad_off,
-    const double* __restrict__ pc, const int64_t* __restrict__ pc_off,
-    const double* __restrict__ thr2v, int n1max, int ld, uint8_t* __restrict__ mask,
-    int32_t* __restrict__ rowcount) {
-  const int b = blockIdx.z;
-  const int64_t c0 = cad_off[b], p0 = pc_off[b];
-  const int n1 = (int)(cad_off[b + 1] - c0);
-  const int n2 = (int)(pc_off[b + 1] - p0);
-  const double thr2 = thr2v[b];
-  const int lane = pk::lane_id();
-  const int j0 = blockIdx.x * kColsPerWave + lane * kColsPerLane;
-  const int row0 = blockIdx.y * kRowsPerBlock + pk::wave_id() * kRowsPerWave;
-  if (row0 >= n1max) return;
-
-  double qx[kColsPerLane], qy[kColsPerLane], qz[kColsPerLane];
-#pragma unroll
-  for (int c = 0; c < kColsPerLane; ++c) {
-    const int j = j0 + c;
-    if (j < n2) {
-      const double* q = pc + (p0 + j) * 3;
-      qx[c] = q[0];
-      qy[c] = q[1];
-      qz[c] = q[2];
-    } else {
-      qx[c] = qy[c] = qz[c] = __builtin_huge_val();  // never within (inf - x = inf)
-    }
-  }
-
-  for (int r = 0; r < kRowsPerWave; ++r) {
-    const int i = row0 + r;
-    if (i >= n1max) break;
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-    int cnt = 0;
-    if (i < n1) {
-      const double* a = cad + (c0 + i) * 3;
-      const double ax = a[0], ay = a[1], az = a[2];
-#pragma unroll
-      for (int c = 0; c < kColsPerLane; ++c) {
-        const bool in = within(ax, ay, az, qx[c], qy[c], qz[c], thr2);
-        w[c >> 2] |= (in ? 1u : 0u) << ((c & 3) * 8);
-        cnt += in ? 1 : 0;
-      }
-    }
-    if (mask != nullptr && j0 < ld) {
-      uint4* dst = reinterpret_cast<uint4*>(mask + ((int64_t)b * n1max + i) * ld + j0);
-      *dst = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    cnt = pk::wave_sum_i32(cnt);
-    if (lane == 0 && cnt != 0) atomicAdd(rowcount + (int64_t)b * n1max + i, cnt);
-  }
-}
-
-// fp32-screened variant (the default). Coordinates are centred on the crop's first CAD
+// fp32-screened kernel (crops the streaming kernel below does not take). Coordinates are centred on the crop's first CAD
 // point in fp64 and rounded to fp32 once per point. Each pair's squared distance is
 // evaluated in fp32 by the expansion s32 = (|a|² + |b|²) - 2 a·b (one add + three FMAs
 // with -2b and |b|² precomputed per column) and classified against
@@ -234,7 +178,6 @@ __device__ __forceinline__ float next_up(float x) {  // nextafter(x, +inf) for f
   return __uint_as_float(x > 0.f ? b + 1u : b - 1u);
 }
 
-template <bool NT>  // NT: nontemporal mask stores (the product choice)
 __global__ __launch_bounds__(kBqThreads) void bq_mask_stream_kernel(
     const double* __restrict__ cad, const int64_t* __restrict__ cad_off,
     const double* __restrict__ pc, const int64_t* __restrict__ pc_off,
@@ -390,11 +333,7 @@ __global__ __launch_bounds__(kBqThreads) void bq_mask_stream_kernel(
         cnt[r] = __builtin_amdgcn_sad_u8(w[0] + w[1] + w[2] + w[3], 0u, cnt[r]);
         if (store) {
           const u32x4 val = {w[0], w[1], w[2], w[3]};
-          if constexpr (NT) {
-            __builtin_nontemporal_store(val, reinterpret_cast<u32x4*>(rowp + (int64_t)r * ld));
-          } else {
-            *reinterpret_cast<u32x4*>(rowp + (int64_t)r * ld) = val;
-          }
+          __builtin_nontemporal_store(val, reinterpret_cast<u32x4*>(rowp + (int64_t)r * ld));
         }
       }
     }
@@ -409,46 +348,6 @@ __global__ __launch_bounds__(kBqThreads) void bq_mask_stream_kernel(
     if ((lane >> 1) == (rp >> 1)) mine = (lane & 1) ? (t >> 16) : (t & 0xffffu);
   }
   if (lane < kRowsPerWave && row0 + lane < n1max) rowcount[(int64_t)b * n1max + row0 + lane] = (int32_t)mine;
-}
-
-// Count-only variant (no mask); same arithmetic.
-__global__ __launch_bounds__(kBqThreads) void bq_count_kernel(
-    const double* __restrict__ cad, const int64_t* __restrict__ cad_off,
-    const double* __restrict__ pc, const int64_t* __restrict__ pc_off,
-    const double* __restrict__ thr2v, int n1max, int32_t* __restrict__ rowcount) {
-  const int b = blockIdx.z;
-  const int64_t c0 = cad_off[b], p0 = pc_off[b];
-  const int n1 = (int)(cad_off[b + 1] - c0);
-  const int n2 = (int)(pc_off[b + 1] - p0);
-  const double thr2 = thr2v[b];
-  const int lane = pk::lane_id();
-  const int j0 = blockIdx.x * kColsPerWave + lane * kColsPerLane;
-  const int row0 = blockIdx.y * kRowsPerBlock + pk::wave_id() * kRowsPerWave;
-  if (row0 >= n1) return;
-  double qx[kColsPerLane], qy[kColsPerLane], qz[kColsPerLane];
-#pragma unroll
-  for (int c = 0; c < kColsPerLane; ++c) {
-    const int j = j0 + c;
-    if (j < n2) {
-      const double* q = pc + (p0 + j) * 3;
-      qx[c] = q[0];
-      qy[c] = q[1];
-      qz[c] = q[2];
-    } else {
-      qx[c] = qy[c] = qz[c] = __builtin_huge_val();
-    }
-  }
-  for (int r = 0; r < kRowsPerWave; ++r) {
-    const int i = row0 + r;
-    if (i >= n1) break;
-    const double* a = cad + (c0 + i) * 3;
-    const double ax = a[0], ay = a[1], az = a[2];
-    int cnt = 0;
-#pragma unroll
-    for (int c = 0; c < kColsPerLane; ++c) cnt += within(ax, ay, az, qx[c], qy[c], qz[c], thr2) ? 1 : 0;
-    cnt = pk::wave_sum_i32(cnt);
-    if (lane == 0 && cnt != 0) atomicAdd(rowcount + (int64_t)b * n1max + i, cnt);
-  }
 }
 
 // Exclusive scan of row counts per crop. grid (B), block 1024.
@@ -568,21 +467,8 @@ extern "C" int pk_ball_query_mask(const double* cad, const int64_t* cad_off, con
   hipStream_t s = pk::as_stream(stream);
   const int nrb = (n1max + kRowsPerBlock - 1) / kRowsPerBlock;
   if (n2max < 65536 && (int64_t)nrb * B < (1ll << 31)) {
-#define PK_BQS(NT)                                                                              \
-  hipLaunchKernelGGL((bq_mask_stream_kernel<NT>), dim3(nrb * B), dim3(kBqThreads), 0, s, cad, cad_off, \
-                     pc, pc_off, thr2, n1max, ld, nrb, mask, rowcount)
-#ifdef PK_DEVBUILD
-    // PK_BQ_VAR=1: plain mask stores (A/B only: 0.40 vs 0.56 of HBM peak for nt, profiles/r06_bq_ramp.txt)
-    static const int var = [] { const char* e = std::getenv("PK_BQ_VAR"); return e ? std::atoi(e) : 0; }();
-    if (var == 1) {
-      PK_BQS(false);
-    } else {
-      PK_BQS(true);
-    }
-#else
-    PK_BQS(true);
-#endif
-#undef PK_BQS
+    hipLaunchKernelGGL(bq_mask_stream_kernel, dim3(nrb * B), dim3(kBqThreads), 0, s, cad, cad_off, pc, pc_off, thr2,
+                       n1max, ld, nrb, mask, rowcount);
   } else {
     dim3 grid(nrb, B);
     hipLaunchKernelGGL(bq_mask_f32_kernel, grid, dim3(kBqThreads), 0, s, cad, cad_off, pc, pc_off,
@@ -591,38 +477,6 @@ extern "C" int pk_ball_query_mask(const double* cad, const int64_t* cad_off, con
   PK_CHECK_LAUNCH();
   return PK_OK;
 }
-
-#ifdef PK_DEVBUILD
-// Development hook (not in include/posekern.h): the previous fp32-screen kernel, for A/B timing.
-extern "C" int pkdev_ball_query_mask_v1(const double* cad, const int64_t* cad_off, const double* pc,
-                                        const int64_t* pc_off, const double* thr2, int B, int n1max,
-                                        int n2max, uint8_t* mask, int ld, int32_t* rowcount,
-                                        void* stream) {
-  hipStream_t s = pk::as_stream(stream);
-  dim3 grid((n1max + kRowsPerBlock - 1) / kRowsPerBlock, B);
-  hipLaunchKernelGGL(bq_mask_f32_kernel, grid, dim3(kBqThreads), 0, s, cad, cad_off, pc, pc_off,
-                     thr2, n1max, ld, mask, rowcount);
-  PK_CHECK_LAUNCH();
-  return PK_OK;
-}
-#endif  // PK_DEVBUILD
-
-#ifdef PK_DEVBUILD
-// Development hook (not in include/posekern.h): the all-fp64 mask kernel, for A/B timing.
-extern "C" int pkdev_ball_query_mask64(const double* cad, const int64_t* cad_off, const double* pc,
-                                       const int64_t* pc_off, const double* thr2, int B, int n1max,
-                                       int n2max, uint8_t* mask, int ld, int32_t* rowcount,
-                                       void* stream) {
-  hipStream_t s = pk::as_stream(stream);
-  hipError_t e = pk::zero_async(rowcount, sizeof(int32_t) * (size_t)B * n1max, s);
-  if (e != hipSuccess) return (int)e;
-  dim3 grid((ld + kColsPerWave - 1) / kColsPerWave, (n1max + kRowsPerBlock - 1) / kRowsPerBlock, B);
-  hipLaunchKernelGGL(bq_mask_kernel, grid, dim3(kBqThreads), 0, s, cad, cad_off, pc, pc_off, thr2,
-                     n1max, ld, mask, rowcount);
-  PK_CHECK_LAUNCH();
-  return PK_OK;
-}
-#endif  // PK_DEVBUILD
 
 extern "C" int pk_ball_query_pairs(const double* cad, const int64_t* cad_off, const double* pc,
                                    const int64_t* pc_off, const double* thr2, int B, int n1max,

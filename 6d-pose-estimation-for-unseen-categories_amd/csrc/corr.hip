@@ -63,103 +63,14 @@ __global__ __launch_bounds__(256) void rigid_score_kernel(const int64_t* __restr
   if (jj < n) score[(int64_t)b * ldl + jj] = acc / (float)n;
 }
 
-// Symmetric scoring: the pair term |‖CAD_i − CAD_j‖ − ‖PC_i − PC_j‖| is the same for (i, j) and
-// (j, i), so each unordered pair is evaluated once (two sqrt per pair instead of four). Grid
-// (T (T + 1) / 2, B) over 64 x 64 tile pairs I <= J of the current list (T = ceil(nmax / 64));
-// block 256 = 16 x 16 threads, 4 x 4 pairs each. A block writes, for every list entry x of tile
-// I, the sum over tile J (part[b][J][x]) and, when I != J, for every entry of tile J the sum over
-// tile I (part[b][I][x]): each (tile, entry) slot is written exactly once, and rigid_reduce_kernel
-// adds the slots in tile order (deterministic).
-constexpr int kRT = 64;
-__global__ __launch_bounds__(256) void rigid_pair_kernel(const int64_t* __restrict__ list, int ldl,
-                                                         const int32_t* __restrict__ nlist,
-                                                         const int64_t* __restrict__ cand, int ldc,
-                                                         const float* __restrict__ cad, int ldcad,
-                                                         const float* __restrict__ pc, int ldpc, int T,
-                                                         float* __restrict__ part) {
-  __shared__ float si[kRT][7], sj[kRT][7];
-  __shared__ float red[16][kRT + 1];
-  const int b = blockIdx.y;
-  const int n = nlist[b];
-  const int t = blockIdx.x;
-  int J = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
-  while ((J + 1) * (J + 2) / 2 <= t) ++J;
-  while (J * (J + 1) / 2 > t) --J;
-  const int I = t - J * (J + 1) / 2;
-  if (J * kRT >= n) return;  // block-uniform: tile outside this round's list
-  const int64_t* L = list + (int64_t)b * ldl;
-  const int64_t* Cd = cand + (int64_t)b * ldc * 2;
-  const float* CA = cad + (int64_t)b * ldcad * 3;
-  const float* PCb = pc + (int64_t)b * ldpc * 3;
-  const int tid = threadIdx.x;
-  if (tid < 2 * kRT) {
-    const int e = tid & (kRT - 1);
-    const int x = (tid < kRT ? I : J) * kRT + e;
-    float (*dst)[7] = tid < kRT ? si : sj;
-    if (x < n) {
-      const int64_t k = L[x];
-      const int64_t c = Cd[2 * k], q = Cd[2 * k + 1];
-      dst[e][0] = CA[3 * c]; dst[e][1] = CA[3 * c + 1]; dst[e][2] = CA[3 * c + 2];
-      dst[e][3] = PCb[3 * q]; dst[e][4] = PCb[3 * q + 1]; dst[e][5] = PCb[3 * q + 2];
-      dst[e][6] = 1.f;
-    } else {
-      dst[e][0] = dst[e][1] = dst[e][2] = dst[e][3] = dst[e][4] = dst[e][5] = 0.f;
-      dst[e][6] = 0.f;
-    }
-  }
-  __syncthreads();
-  const int tx = tid & 15, ty = tid >> 4;
-  float ra[4] = {0.f, 0.f, 0.f, 0.f}, ca[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int i = ty * 4 + r;
-    const float ax = si[i][0], ay = si[i][1], az = si[i][2], px = si[i][3], py = si[i][4], pz = si[i][5];
-    const float vi = si[i][6];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int j = tx * 4 + c;
-      const float dx = sj[j][0] - ax, dy = sj[j][1] - ay, dz = sj[j][2] - az;
-      const float ex = sj[j][3] - px, ey = sj[j][4] - py, ez = sj[j][5] - pz;
-      const float a = __builtin_amdgcn_sqrtf((dx * dx + dy * dy) + dz * dz);
-      const float bb = __builtin_amdgcn_sqrtf((ex * ex + ey * ey) + ez * ez);
-      const float v = fabsf(a - bb) * (vi * sj[j][6]);  // invalid entries contribute 0
-      ra[r] += v;
-      ca[c] += v;
-    }
-  }
-  float* P = part + (int64_t)b * T * ldl;
-  // row sums of tile I over tile J: reduce over tx in order
-#pragma unroll
-  for (int r = 0; r < 4; ++r) red[tx][ty * 4 + r] = ra[r];
-  __syncthreads();
-  if (tid < kRT) {
-    float acc = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc += red[q][tid];
-    const int x = I * kRT + tid;
-    if (x < n) P[(int64_t)J * ldl + x] = acc;
-  }
-  if (I == J) return;  // block-uniform; the diagonal tile's row sums already cover both orders
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < 4; ++c) red[ty][tx * 4 + c] = ca[c];
-  __syncthreads();
-  if (tid < kRT) {
-    float acc = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc += red[q][tid];
-    const int x = J * kRT + tid;
-    if (x < n) P[(int64_t)I * ldl + x] = acc;
-  }
-}
-
-// ---- Packed coordinates, 128 x 128 pair tiles (rounds 2 and 3 of the filter).
-// Round 2's rigid_pair_kernel spent most of a block on its prologue: every entry of both tiles
-// was a dependent gather list -> cand -> cad / pc (three global loads in a chain) for only 16
-// pairs per thread. Here the coordinates of the current list live in a packed array (one
-// 32-B record per entry: {cad_x, pc_x, cad_y, pc_y, cad_z, pc_z, valid, 0}); the first round's is
-// gathered once (rigid_gather_kernel) and each compaction carries the survivors' records
-// along (rigid_compact_pts_kernel), so a pair block loads its two tiles with plain 16-B loads.
+// ---- Packed coordinates, symmetric scoring over 256 x 256 pair tiles (rounds 2 and 3 of the filter).
+// The pair term |‖CAD_i − CAD_j‖ − ‖PC_i − PC_j‖| is the same for (i, j) and (j, i), so each
+// unordered pair is evaluated once (two sqrt per pair instead of four), tile pair by tile pair.
+// The coordinates of the current list live in a packed array (one 32-B record per entry:
+// {cad_x, pc_x, cad_y, pc_y, cad_z, pc_z, valid, 0}) instead of behind the dependent gather
+// list -> cand -> cad / pc; the first round's is gathered once (rigid_gather_kernel) and each
+// compaction carries the survivors' records along (rigid_compact_pts_kernel), so a pair block
+// loads its two tiles with plain 16-B loads.
 // The pair term is two rigid_dist (FMA sums of squares, v_sqrt_f32) and |a - b| folded into the
 // row and column sums as a source modifier; kPS x kPS (16 x 16) pairs per thread.
 constexpr int kRT2 = 256;            // entries per tile (rounds 2, 3)
@@ -270,7 +181,7 @@ __device__ __forceinline__ void rigid_tile_pairs_tab(const RigidRec* __restrict_
 constexpr int kTab = 8192;  // run-pair table entries (32 KB of LDS)
 
 // Grid (T (T + 1) / 2, B) over kRT2 x kRT2 tile pairs I <= J (T = ceil(nmax / kRT2)), XCD-aware
-// (a crop's tile pairs share one XCD's L2); block 256 = 16 x 16 threads. As rigid_pair_kernel:
+// (a crop's tile pairs share one XCD's L2); block 256 = 16 x 16 threads. A block writes
 // part[b][J][x] = sum over tile J of entry x of tile I, and for I != J part[b][I][y] for the
 // entries y of tile J; every slot written once, summed in tile order by rigid_reduce_kernel.
 // Fixed-order reductions (16-lane butterflies, then the 4 waves' column partials in wave order).
@@ -1054,7 +965,7 @@ __global__ __launch_bounds__(64) void cgt_solve_kernel(const double* __restrict_
 
 }  // namespace
 
-// scratch: the tile partials [B][T][ldc] f32 (T = ceil(nmax / 128)), then two packed-record
+// scratch: the tile partials [B][T][ldc] f32 (T = ceil(nmax / kRT2)), then two packed-record
 // arrays [B][ldc] (the current and the next round's list), 16-B aligned
 static int64_t rigid_part_bytes(int B, int nmax, int ldc) {
   const int64_t b = (int64_t)B * ((nmax + kRT2 - 1) / kRT2) * ldc * (int64_t)sizeof(float);
@@ -1062,23 +973,20 @@ static int64_t rigid_part_bytes(int B, int nmax, int ldc) {
 }
 
 #ifdef PK_DEVBUILD
-static int g_rigid_variant = 0;  // pkdev_rigidity_variant (A/B timing): 1 round 2's 64-tile gather path,
-                                 // 2 round 3's ungrouped first round, 3 no run-pair crop tables
+static int g_rigid_variant = 0;  // pkdev_rigidity_variant: 3 = no run-pair crop tables (the bit-identity test)
 #else
 constexpr int g_rigid_variant = 0;
 #endif
 
 extern "C" int64_t pk_rigidity_filter_work_size(int B, int nmax, int ldc) {
   if (B <= 0 || nmax <= 0) return 0;
-  const int64_t v2 = rigid_part_bytes(B, nmax, ldc) + 2 * (int64_t)B * ldc * (int64_t)sizeof(RigidRec);
-  const int64_t v1 = (int64_t)B * ((nmax + kRT - 1) / kRT) * ldc * (int64_t)sizeof(float);
-  return v2 > v1 ? v2 : v1;
+  return rigid_part_bytes(B, nmax, ldc) + 2 * (int64_t)B * ldc * (int64_t)sizeof(RigidRec);
 }
 
 #ifdef PK_DEVBUILD
 extern "C" int pkdev_rigidity_variant(int v) {
   const int old = g_rigid_variant;
-  if (v >= 0) g_rigid_variant = v;
+  if (v == 0 || v == 3) g_rigid_variant = v;
   return old;
 }
 #endif  // PK_DEVBUILD
@@ -1094,7 +1002,7 @@ extern "C" int pk_rigidity_filter(const int64_t* cand, int ldc, const int32_t* n
   const dim3 g((nmax + 255) / 256, B);
   const int T2 = (nmax + kRT2 - 1) / kRT2;
   const int T1 = (nmax + kRG - 1) / kRG;  // <= T2: the grouped round's partial rows fit
-  const bool packed = partial != nullptr && T2 > 0 && g_rigid_variant != 1;
+  const bool packed = partial != nullptr && T2 > 0;
   RigidRec* pa = nullptr;
   RigidRec* pb = nullptr;
   if (packed) {
@@ -1110,19 +1018,18 @@ extern "C" int pk_rigidity_filter(const int64_t* cand, int ldc, const int32_t* n
   int64_t* lout = list_b;
   int32_t* nout = n_b;
   int32_t* nspare = n_a;
-  const int T = (nmax + kRT - 1) / kRT;
   for (int r = 0; r < 3; ++r) {
-    if (packed && r == 0 && g_rigid_variant != 2) {  // grouped first round (T1 <= T2 partial rows)
-      hipLaunchKernelGGL(rigid_group_kernel, dim3(T1 * (T1 + 1) / 2, B), dim3(256), 0, s, nin, ldc, pa, T1, partial);
-      PK_CHECK_LAUNCH();
-      hipLaunchKernelGGL(rigid_reduce_kernel, g, dim3(256), 0, s, nin, ldc, partial, T1, kRG, score);
-    } else if (packed) {
-      hipLaunchKernelGGL(rigid_pair2_kernel, dim3(T2 * (T2 + 1) / 2, B), dim3(256), 0, s, nin, ldc, pa, T2, partial,
-                         (int)(g_rigid_variant != 3));
-      PK_CHECK_LAUNCH();
-      hipLaunchKernelGGL(rigid_reduce_kernel, g, dim3(256), 0, s, nin, ldc, partial, T2, kRT2, score);
-    }
     if (packed) {
+      if (r == 0) {  // grouped first round (T1 <= T2 partial rows)
+        hipLaunchKernelGGL(rigid_group_kernel, dim3(T1 * (T1 + 1) / 2, B), dim3(256), 0, s, nin, ldc, pa, T1, partial);
+        PK_CHECK_LAUNCH();
+        hipLaunchKernelGGL(rigid_reduce_kernel, g, dim3(256), 0, s, nin, ldc, partial, T1, kRG, score);
+      } else {
+        hipLaunchKernelGGL(rigid_pair2_kernel, dim3(T2 * (T2 + 1) / 2, B), dim3(256), 0, s, nin, ldc, pa, T2, partial,
+                           (int)(g_rigid_variant != 3));
+        PK_CHECK_LAUNCH();
+        hipLaunchKernelGGL(rigid_reduce_kernel, g, dim3(256), 0, s, nin, ldc, partial, T2, kRT2, score);
+      }
       PK_CHECK_LAUNCH();
       hipLaunchKernelGGL(rigid_compact_pts_kernel, dim3(B), dim3(1024), 0, s, lin, ldc, nin, score, thr4, r, pa, lout,
                          r < 2 ? pb : nullptr, nout);
@@ -1130,17 +1037,10 @@ extern "C" int pk_rigidity_filter(const int64_t* cand, int ldc, const int32_t* n
       RigidRec* tp = pa;
       pa = pb;
       pb = tp;
-    } else if (partial && T > 0) {  // round 2: symmetric 64-tiles with gathers, ordered reduction
-      hipLaunchKernelGGL(rigid_pair_kernel, dim3(T * (T + 1) / 2, B), dim3(256), 0, s, lin, ldc, nin, cand, ldc, cad,
-                         ldcad, pc, ldpc, T, partial);
-      PK_CHECK_LAUNCH();
-      hipLaunchKernelGGL(rigid_reduce_kernel, g, dim3(256), 0, s, nin, ldc, partial, T, kRT, score);
-    } else {
+    } else {  // no scratch: every candidate's score against the whole list, gathered through cand
       hipLaunchKernelGGL(rigid_score_kernel, g, dim3(256), 0, s, lin, ldc, nin, cand, ldc, cad, ldcad, pc, ldpc,
                          score);
-    }
-    PK_CHECK_LAUNCH();
-    if (!packed) {
+      PK_CHECK_LAUNCH();
       hipLaunchKernelGGL(rigid_compact_kernel, dim3(B), dim3(1024), 0, s, lin, ldc, nin, score, thr4, r, lout,
                          nout);
       PK_CHECK_LAUNCH();

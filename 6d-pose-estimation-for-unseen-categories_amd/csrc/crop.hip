@@ -52,20 +52,6 @@ __device__ __forceinline__ bool eroded(const uint8_t* __restrict__ m, int H, int
   return true;
 }
 
-// grid (H, F), block 256: count eroded pixels per image row.
-__global__ __launch_bounds__(256) void bp_count_kernel(const uint8_t* __restrict__ mask, int H, int W,
-                                                       int32_t* __restrict__ rowcnt) {
-  const int v = blockIdx.x, f = blockIdx.y;
-  const uint8_t* m = mask + (int64_t)f * H * W;
-  int c = 0;
-  for (int u = threadIdx.x; u < W; u += blockDim.x) c += eroded(m, H, W, v, u) ? 1 : 0;
-  c = pk::wave_sum_i32_s(c);
-  __shared__ int ws[4];
-  if (pk::lane_id() == 0) ws[pk::wave_id()] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) rowcnt[(int64_t)f * H + v] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-
 // Generic per-segment exclusive scan of int32 counts -> int64 offsets (+ totals).
 // grid (S), block 1024; segment s covers cnt[s*n .. s*n+n).
 __global__ __launch_bounds__(1024) void seg_scan_kernel(const int32_t* __restrict__ cnt, int n,
@@ -103,48 +89,10 @@ __global__ void offsets_kernel(const int64_t* __restrict__ counts, int B, int64_
   }
 }
 
-// grid (H, F), block 64 (one wave walks the row in 64-pixel chunks, ordered by ballot).
-__global__ __launch_bounds__(64) void bp_write_kernel(
-    const uint16_t* __restrict__ depth, const uint8_t* __restrict__ mask, int H, int W,
-    const double* __restrict__ K, const float* __restrict__ cam_scale,
-    const int64_t* __restrict__ rowoff, const int64_t* __restrict__ frame_off, double* __restrict__ out,
-    int64_t cap, int32_t* __restrict__ pix, int32_t* __restrict__ idxmap) {
-  const int v = blockIdx.x, f = blockIdx.y;
-  const uint8_t* m = mask + (int64_t)f * H * W;
-  const uint16_t* d = depth + (int64_t)f * H * W;
-  const double fx = K[f * 9 + 0], cx = K[f * 9 + 2], fy = K[f * 9 + 4], cy = K[f * 9 + 5];
-  const float cs = cam_scale[f];
-  int64_t o = frame_off[f] + rowoff[(int64_t)f * H + v];
-  const int lane = threadIdx.x;
-  for (int u0 = 0; u0 < W; u0 += 64) {
-    const int u = u0 + lane;
-    const bool keep = u < W && eroded(m, H, W, v, u);
-    const uint64_t bal = __ballot(keep);
-    if (idxmap != nullptr && u < W)
-      idxmap[(int64_t)f * H * W + (int64_t)v * W + u] =
-          keep ? (int32_t)(o - frame_off[f] + __popcll(bal & ((1ull << lane) - 1ull))) : -1;
-    if (keep) {
-      const int64_t w = o + __popcll(bal & ((1ull << lane) - 1ull));
-      if (pix != nullptr && w < cap) pix[w] = v * W + u;
-      if (w < cap) {
-        const float z32 = (float)d[(int64_t)v * W + u] / cs;  // f32 / f32, correctly rounded
-        const double z = (double)z32;
-        const double X = (((double)u - cx) * z) / fx;
-        const double Y = (((double)v - cy) * z) / fy;
-        out[3 * w + 0] = X * 100.0;
-        out[3 * w + 1] = Y * 100.0;
-        out[3 * w + 2] = z * 100.0;
-      }
-    }
-    o += __popcll(bal);
-  }
-}
-
-// ---- Round 5: one wave per image row, 16 consecutive pixels per lane (64 x 16 = 1024-pixel
+// ---- Backprojection: one wave per image row, 16 consecutive pixels per lane (64 x 16 = 1024-pixel
 // segments), the erosion of the lane's pixels as bit operations on three rows' is-255 masks.
 // Every mask / depth load of a segment is issued at once (16-B vectors when the rows are
-// 16-B aligned): round 4's kernels walked a row in 64-pixel chunks, five dependent byte loads
-// each, one block per row (15,360 blocks of one wave at 640 x 480 x 32).
+// 16-B aligned) instead of five dependent byte loads per pixel.
 constexpr int kBpPx = 16;
 struct BpRow {  // bit c: pixel u0 + c of the segment
   uint32_t keep;  // eroded (255 with every in-image 4-neighbour 255)
@@ -302,17 +250,6 @@ __device__ __forceinline__ void topk_insert_nth(double (&best)[kKnn], double v) 
   if constexpr (t < kKnn) best[t] = v;
 }
 
-#ifdef PK_DEVBUILD
-__device__ __forceinline__ void topk_insert_r6(double (&best)[kKnn], double v) {
-#pragma unroll
-  for (int k = 0; k < kKnn; ++k) {
-    const double lo = fmin(best[k], v), hi = fmax(best[k], v);
-    best[k] = lo;
-    v = hi;
-  }
-}
-#endif
-
 __device__ __forceinline__ double sqdist(double ax, double ay, double az, const double* b) {
   const double dx = ax - b[0], dy = ay - b[1], dz = az - b[2];
   return (dx * dx + dy * dy) + dz * dz;  // nanoflann L2: ((dx²+dy²)+dz²)
@@ -336,13 +273,8 @@ __device__ __forceinline__ double sqdist(double ax, double ay, double az, const 
 // The kept set is a superset of the true knn nearest (ties included), so the sorted
 // top-knn values are exactly those of a full brute-force search.
 constexpr int kSorMaxBox = 1024;
-#ifndef PK_SOR_BATCH
-#define PK_SOR_BATCH 4
-#endif
-#ifndef PK_SOR_MINW
-#define PK_SOR_MINW 4
-#endif
-constexpr int kSorBatch = PK_SOR_BATCH;  // pixels of a window row gathered together (loads in flight at once)
+constexpr int kSorMinW = 4;   // the kNN kernel's second __launch_bounds__ argument
+constexpr int kSorBatch = 4;  // pixels of a window row gathered together (loads in flight at once)
 
 // distances from the query to the points of pixels uu .. min(uu + 7, u1) of an index-map row;
 // bit t of the result: pixel uu + t holds a point (s[t] valid). All index loads, then all
@@ -466,7 +398,7 @@ __device__ __forceinline__ double sor_mean(const double (&best)[kKnn], int kk) {
 // list with guarded insertions. Splitting the border queries off into waves of their own after a barrier
 // was measured slower: every workgroup is resident at once, so the kernel
 // takes as long as its longest chain of dependent gathers, and that chain is a border query's.
-__global__ __launch_bounds__(kSorThreads, PK_SOR_MINW) void sor_knn_kernel(const double* __restrict__ xyz,
+__global__ __launch_bounds__(kSorThreads, kSorMinW) void sor_knn_kernel(const double* __restrict__ xyz,
                                                                  const int64_t* __restrict__ off, int knn,
                                                                  const int32_t* __restrict__ pix,
                                                                  const int32_t* __restrict__ idxmap, int H, int W,
@@ -576,159 +508,6 @@ __global__ __launch_bounds__(kSorThreads, PK_SOR_MINW) void sor_knn_kernel(const
   }
   if (act) avg[base + i] = sor_mean(best, kk);
 }
-
-#ifdef PK_DEVBUILD
-// Development A/B (PK_SOR_OLD=1): the round-6 kernel, every query handled by its own thread.
-
-__global__ __launch_bounds__(kSorThreads, PK_SOR_MINW) void sor_knn_kernel_r6(const double* __restrict__ xyz,
-                                                                 const int64_t* __restrict__ off, int knn,
-                                                                 const int32_t* __restrict__ pix,
-                                                                 const int32_t* __restrict__ idxmap, int H, int W,
-                                                                 const double* __restrict__ Kmat, int tiles, int B,
-                                                                 double* __restrict__ avg, int prio) {
-  pk::set_wave_prio(prio);
-  __shared__ float4 tile[kSorTile];
-  {
-  const int item = blockIdx.x;
-  const int b = item % B, bx = item / B;
-  const int64_t base = off[b];
-  const int n = (int)(off[b + 1] - base);
-  const int i = bx * kSorThreads + threadIdx.x;
-  if (bx * kSorThreads >= n) return;  // workgroup-uniform
-  const bool act = i < n;
-  const double* p = xyz + base * 3;
-  const double ox = p[0], oy = p[1], oz = p[2];
-  double q0 = 0.0, q1 = 0.0, q2 = 0.0;
-  if (act) {
-    q0 = p[3 * i];
-    q1 = p[3 * i + 1];
-    q2 = p[3 * i + 2];
-  }
-  const int kk = knn < n ? knn : n;
-  double best[kKnn];
-#pragma unroll
-  for (int k = 0; k < kKnn; ++k) best[k] = __builtin_huge_val();
-  double T = __builtin_huge_val();
-  bool done = false;
-  if (act && pix != nullptr && idxmap != nullptr) {
-    const int pp = pix[base + i];
-    const int v = pp / W, u = pp % W;
-    const int32_t* im = idxmap + (int64_t)b * H * W;
-    int found = 0, Rw = -1;
-    for (int R = 2; R <= 8; R *= 2) {  // 5x5, then 9x9, 17x17 near the mask border
-      found = 0;
-#pragma unroll
-      for (int k = 0; k < kKnn; ++k) best[k] = __builtin_huge_val();
-      for (int vv = max(v - R, 0); vv <= min(v + R, H - 1); ++vv) {
-        const int32_t* row = im + vv * W;
-        const int u1 = min(u + R, W - 1);
-        for (int uu = max(u - R, 0); uu <= u1; uu += kSorBatch) {
-          double s[kSorBatch];
-          const int m = sor_gather(row, uu, u1, p, q0, q1, q2, s);
-#pragma unroll
-          for (int t = 0; t < kSorBatch; ++t)
-            if ((m >> t) & 1) topk_insert_r6(best, s[t]);
-          found += __builtin_popcount(m);
-        }
-      }
-      if (found >= kk) {
-        Rw = R;
-        break;
-      }
-    }
-    if (Rw >= 0) {
-#pragma unroll
-      for (int k = 0; k < kKnn; ++k)
-        if (k == kk - 1) T = best[k];  // static register index (no scratch)
-    }
-    // pass 2a: best keeps the window's kk smallest (all <= T, real points), and the box scan
-    // adds the box pixels outside that window: the kk smallest of window + box are exact
-    bool box = false;
-    int u0 = 0, u1 = -1, v0 = 0, v1 = -1;
-    if (Kmat != nullptr && T < __builtin_huge_val()) {
-      const double* Kb = Kmat + 9 * b;
-      const double fx = Kb[0], cx = Kb[2], fy = Kb[4], cy = Kb[5];
-      const double r = sqrt(T) * (1.0 + 1e-9) + 1e-300;
-      if (fx > 0.0 && fy > 0.0 && q2 > r) {
-        // a candidate c within r of q: |X_q/Z_q - X_c/Z_c| <= (r/Z_q) sqrt(1 + t_c^2) (Cauchy-
-        // Schwarz on (X_q - X_c) + t_c (Z_c - Z_q)), with |t_c| <= the image bound tx and
-        // |t_c| <= (|t_q| + rho) / (1 - rho), rho = r / Z_q (SOR camera box)
-        const double rho = r / q2;
-        const double tx = fmin(fmax(fabs(cx), fabs((double)(W - 1) - cx)) / fx, (fabs(q0 / q2) + rho) / (1.0 - rho));
-        const double ty = fmin(fmax(fabs(cy), fabs((double)(H - 1) - cy)) / fy, (fabs(q1 / q2) + rho) / (1.0 - rho));
-        const double bu = fx * rho * sqrt(1.0 + tx * tx), bv = fy * rho * sqrt(1.0 + ty * ty);
-        if (bu < 64.0 && bv < 64.0) {
-          const int ru = (int)ceil(bu * (1.0 + 1e-9)) + 1, rv = (int)ceil(bv * (1.0 + 1e-9)) + 1;
-          if ((2 * ru + 1) * (2 * rv + 1) <= kSorMaxBox) {
-            box = true;
-            v0 = max(v - rv, 0);
-            v1 = min(v + rv, H - 1);
-            u0 = max(u - ru, 0);
-            u1 = min(u + ru, W - 1);
-          }
-        }
-      }
-    }
-    if (box) {
-      for (int vv = v0; vv <= v1; ++vv) {
-        const int32_t* row = im + vv * W;
-        const bool in_w = vv >= v - Rw && vv <= v + Rw;  // this row's window pixels are in best
-        for (int seg = 0; seg < 2; ++seg) {
-          const int a = in_w ? (seg == 0 ? u0 : max(u0, u + Rw + 1)) : (seg == 0 ? u0 : 1);
-          const int c = in_w ? (seg == 0 ? min(u1, u - Rw - 1) : u1) : (seg == 0 ? u1 : 0);
-          for (int uu = a; uu <= c; uu += kSorBatch) {
-            double s[kSorBatch];
-            const int m = sor_gather(row, uu, c, p, q0, q1, q2, s);
-#pragma unroll
-            for (int t = 0; t < kSorBatch; ++t)
-              if (((m >> t) & 1) && s[t] <= T && s[t] < best[kKnn - 1]) topk_insert_r6(best, s[t]);
-          }
-        }
-      }
-      done = true;
-    } else {
-#pragma unroll
-      for (int k = 0; k < kKnn; ++k) best[k] = __builtin_huge_val();
-    }
-  }
-  if (__syncthreads_or(act && !done)) {
-    const float qx = (float)(q0 - ox), qy = (float)(q1 - oy), qz = (float)(q2 - oz);
-    const float qa = fmaxf(fabsf(qx), fmaxf(fabsf(qy), fabsf(qz)));
-    const float Tf = T == __builtin_huge_val() ? __builtin_huge_valf() : (float)T;
-    for (int t0 = 0; t0 < n; t0 += kSorTile) {
-      const int tn = min(kSorTile, n - t0);
-      __syncthreads();
-      for (int e = threadIdx.x; e < tn; e += kSorThreads) {
-        const double* c = p + 3 * (t0 + e);
-        const float cx = (float)(c[0] - ox), cy = (float)(c[1] - oy), cz = (float)(c[2] - oz);
-        tile[e] = make_float4(cx, cy, cz, fmaxf(fabsf(cx), fmaxf(fabsf(cy), fabsf(cz))));
-      }
-      __syncthreads();
-      if (act && !done) {
-        for (int e = 0; e < tn; ++e) {
-          const float4 c = tile[e];
-          const float dx = qx - c.x, dy = qy - c.y, dz = qz - c.z;
-          const float d32 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-          const float sa = qa + c.w;
-          const float lim = fmaf(1.9073486e-6f, fmaf(sa, sa, Tf), Tf);  // T + 2^-19 (T + S^2)
-          if (d32 <= lim) {
-            const double s = sqdist(q0, q1, q2, p + 3 * (t0 + e));
-            if (s <= T && s < best[kKnn - 1]) topk_insert_r6(best, s);
-          }
-        }
-      }
-    }
-  }
-  if (act) {
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < kKnn; ++k)
-      if (k < kk) acc = acc + sqrt_rn(best[k]);
-    avg[base + i] = kk > 0 ? acc / (double)kk : -1.0;
-  }
-  }
-}
-#endif  // PK_DEVBUILD
 
 // One block per crop: cloud mean over avg > 0, then the Bessel std, accumulated in point
 // order exactly like std::accumulate / std::inner_product: s = s + t_k, k = 0 .. n-1, IEEE
@@ -1170,19 +949,6 @@ extern "C" int pk_sor(const double* xyz, const int64_t* off, int B, int nmax, in
   if (nmax > 0 && !pk::diag_skip("sorknn")) {
     const int tiles = (nmax + kSorThreads - 1) / kSorThreads;
     for (int rep = 0; rep < (pk::diag_twice("sorknn") ? 2 : 1); ++rep) {
-#ifdef PK_DEVBUILD
-      static const bool r6 = [] {  // development knob PK_SOR_OLD=1: the round-6 kernel
-        const char* e = std::getenv("PK_SOR_OLD");
-        return e != nullptr && std::atoi(e) != 0;
-      }();
-      if (r6) {
-        hipLaunchKernelGGL(sor_knn_kernel_r6, dim3((unsigned)((int64_t)tiles * B)), dim3(kSorThreads), 0, s, xyz,
-                           off, knn, pix, idxmap, H, W, pix != nullptr ? K : nullptr, tiles, B, avg,
-                           pk::side_prio());
-        PK_CHECK_LAUNCH();
-        continue;
-      }
-#endif
       hipLaunchKernelGGL(sor_knn_kernel, dim3((unsigned)((int64_t)tiles * B)),
                          dim3(kSorThreads), 0, s, xyz, off, knn, pix, idxmap, H, W,
                          pix != nullptr ? K : nullptr, tiles, B, avg, pk::side_prio());

@@ -28,11 +28,11 @@
 // fragment feeds two accumulation chains). Epilogue per 16 x 16 tile: running argmin / sorted
 // top-5 per column (ties: lowest row); the two row halves merge through LDS at the end. With
 // RS > 1 the blocks' row parts write partial lists that pass 3 merges (same tie rule), so one
-// 4096-point crop (configs[4]) still spreads over the chip. fd_main_kernel (development knob
-// PK_FD_DIRECT=0) is the earlier pass: one column tile per wave, rows staged through an LDS
-// ring shared by the block's 4 waves (measured slower: DESIGN.md §5).
+// 4096-point crop (configs[4]) still spreads over the chip.
+// Mode 0 on 16-byte-aligned operand rows takes the one-pass kernels further down instead
+// (fd_top1_prep_kernel, then fd_top1_kernel / fd_top5_kernel); the two passes above serve modes
+// 1 and 2 and unaligned mode-0 inputs.
 #include <algorithm>
-#include <cstdlib>
 
 #include "common.hpp"
 #include "mfma_tile.hpp"
@@ -43,7 +43,6 @@ constexpr int kF = 30;   // n_fmap
 constexpr int kK = 32;   // contraction length (K padded)
 constexpr int kCW = 1;   // column tiles per wave
 constexpr int kWaves = 4;
-constexpr int kCols = kWaves * kCW * 16;  // columns per block
 constexpr int kCH = 8;   // row tiles per LDS stage
 using pk::f32x4;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
@@ -309,8 +308,7 @@ struct Top1x4 {
   int t[4];
 };
 
-// The main pass without LDS staging (the default; PK_FD_DIRECT=0 selects the LDS-ring pass
-// above). Block = 4 waves = 2 column pairs x 2 row halves: wave (wc, wr) takes column tiles
+// The main pass, without LDS staging. Block = 4 waves = 2 column pairs x 2 row halves: wave (wc, wr) takes column tiles
 // 4 cg + 2 wc and 4 cg + 2 wc + 1 and half wr of the block's row tiles, reading the rows' MFMA
 // fragments straight from L2 into registers one chunk of CHD tiles ahead of the MFMAs (two
 // register buffers: the next chunk's loads are in flight during this chunk's 16 * CHD MFMAs).
@@ -514,36 +512,10 @@ __global__ __launch_bounds__(64 * kWaves) void fd_main_direct_kernel(
 // distance: a column whose best key is <= bits(1e-30) (a zero, tiny or negative expansion) is
 // rescanned for its first row at or below the clamp (wave-uniform, rare: coincident features).
 // With RS > 1 (small batches) the row parts' keys go to scratch and fd_top1_merge_kernel takes
-// the minimum. The development variant PK_FD_VAR=20 forms the emb operands inside the main pass
-// instead (one launch; the round-5 first form, A/B).
+// the minimum.
 constexpr int kTop1CT = 8;
 constexpr int kTop1Waves = 8;  // two per SIMD: one wave's dependency stalls are the other's MFMA time
-#ifdef PK_DEVBUILD
-__device__ unsigned long long g_fd_stamps[4096 * 16];  // (development: VAR 13 phase stamps per block)
-#define FD_STAMP(i, v)                                                  \
-  do {                                                                  \
-    if constexpr (VAR == 13) {                                          \
-      if (threadIdx.x == 0) g_fd_stamps[blockIdx.x * 16 + (i)] = (v);   \
-    }                                                                   \
-  } while (0)
-#else
-#define FD_STAMP(i, v) \
-  do {                 \
-  } while (0)
-#endif
 constexpr int kClampBits = 0x0da24260;  // bits of 1e-30f: clamp_min(1e-30) (cdist mm path)
-
-// -2 C in the emb MFMA's A order: lane (m, gg) holds -2 C[16 n + m][16 h + 4 gg + q] at s = 4 h + q
-__device__ __forceinline__ void top1_cv(const float* __restrict__ Cb, int c16, int g, float (&cv)[2][8]) {
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int s8 = 0; s8 < 8; ++s8) {
-      const int row = 16 * n + c16, f = 16 * (s8 >> 2) + 4 * g + (s8 & 3);
-      const float cval = Cb[min(row, kF - 1) * kF + min(f, kF - 1)];  // (unconditional load)
-      cv[n][s8] = (row < kF && f < kF) ? -2.f * cval : 0.f;
-    }
-}
 
 // x row t*16 + c16 of a crop (a padding row reads row 0: finite, its distance is +inf anyway)
 __device__ __forceinline__ void top1_xload(const float* __restrict__ xb, int ldx, int N1, int t, int c16, int g,
@@ -660,8 +632,7 @@ __global__ __launch_bounds__(512) void fd_top1_prep_kernel(const float* __restri
   asm volatile("" ::"v"(yt[0]), "v"(yt[1]), "v"(yt[2]), "v"(yt[3]));  // (keeps the touch loads)
 }
 
-// pass 2 (EMB: form the emb operands in this pass instead of reading pass 1's tiles)
-template <int VAR = 0, bool EMB = false>
+// pass 2 (ex, ldx and C are not read: the row operands come from pass 1's tiles)
 __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top1_kernel(
     const float* __restrict__ ex, int ldx, const float* __restrict__ C, const f32x4* __restrict__ Atile, int T1,
     const float* __restrict__ ey, int ldy, const int32_t* __restrict__ n1, const int32_t* __restrict__ n2, int V1max,
@@ -685,9 +656,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top1_kernel(
     }
   }
   const int cg = k % NCG, rs = k / NCG;
-  FD_STAMP(0, __builtin_amdgcn_s_memtime());
-  FD_STAMP(5, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4));
-  FD_STAMP(6, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20));
   const int j0 = cg * kTop1CT * 16;
   const int tid = threadIdx.x, lane = pk::lane_id(), w = __builtin_amdgcn_readfirstlane(pk::wave_id());
   // the column operands' loads go out beside the crop sizes' (their addresses do not need them)
@@ -700,29 +668,16 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top1_kernel(
   const int nt = (N1 + 15) >> 4;
   const int Q = RS * kTop1Waves, qw = rs * kTop1Waves + w;
   const int tb = (int)((int64_t)nt * qw / Q), te = (int)((int64_t)nt * (qw + 1) / Q);  // this wave's row tiles
-  const float* xb = ex + (int64_t)b * V1max * ldx;
   const f32x4* Ab = Atile + (int64_t)b * T1 * 128;
-  // the operand of tile t: pass 1's A tile (two 16-B loads per lane), or x rows to embed here
+  // the operand of tile t: pass 1's A tile (two 16-B loads per lane)
   auto opload = [&](int t, float4 (&xv)[2]) {
-    if constexpr (EMB) {
-      top1_xload(xb, ldx, N1, t, c16, g, xv);
-    } else {
-      const f32x4 u0 = Ab[(int64_t)t * 128 + lane], u1 = Ab[(int64_t)t * 128 + 64 + lane];
-      xv[0] = make_float4(u0[0], u0[1], u0[2], u0[3]);
-      xv[1] = make_float4(u1[0], u1[1], u1[2], u1[3]);
-    }
+    const f32x4 u0 = Ab[(int64_t)t * 128 + lane], u1 = Ab[(int64_t)t * 128 + 64 + lane];
+    xv[0] = make_float4(u0[0], u0[1], u0[2], u0[3]);
+    xv[1] = make_float4(u1[0], u1[1], u1[2], u1[3]);
   };
-  float cv[2][8];
-  if constexpr (EMB) top1_cv(C + (int64_t)b * kF * kF, c16, g, cv);
-  auto emb = [&](int t, const float4 (&xv)[2], float (&a)[8]) {
-    if constexpr (EMB) {
-      f32x4 e[2];
-      top1_emb_mfma(cv, xv, e);
-      top1_emb_norm(t, N1, c16, g, e, a);
-    } else {
-      a[0] = xv[0].x, a[1] = xv[0].y, a[2] = xv[0].z, a[3] = xv[0].w;
-      a[4] = xv[1].x, a[5] = xv[1].y, a[6] = xv[1].z, a[7] = xv[1].w;
-    }
+  auto unpack = [](const float4 (&xv)[2], float (&a)[8]) {
+    a[0] = xv[0].x, a[1] = xv[0].y, a[2] = xv[0].z, a[3] = xv[0].w;
+    a[4] = xv[1].x, a[5] = xv[1].y, a[6] = xv[1].z, a[7] = xv[1].w;
   };
   float4 xc[2], xn[2];
   float a[8];
@@ -744,7 +699,7 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top1_kernel(
     }
     sPart[gy][jj] = part_;
     if (j0 >= N2) return;  // (block-uniform; after the loads' consumers, so they are not sunk past it)
-    if (tb < te) emb(tb, xc, a);  // (the first tile's operand while the partials meet)
+    if (tb < te) unpack(xc, a);  // (the first tile's operand while the partials meet)
     __syncthreads();
     if (gy == 3) {  // |y|^2: the lane groups' partials in the order 0, 1, 2, 3
       float nrm = 0.f;
@@ -766,7 +721,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top1_kernel(
         for (int q = 0; q < 4; ++q) bo[c2][4 * h + q] = t4[q];
       }
   }
-  FD_STAMP(1, __builtin_amdgcn_s_memtime());
   int bk[kTop1CT][4], bt[kTop1CT][4];
 #pragma unroll
   for (int c = 0; c < kTop1CT; ++c)
@@ -798,9 +752,9 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top1_kernel(
           [k3] "v"(__float_as_int(acc[3])), [tv] "v"(t));
   };
   // software pipeline: tile t's 8 column tiles in pairs (two accumulation chains each), the
-  // selection of pair p - 1 behind pair p's MFMAs, tile t + 1's operand (loaded two tiles ahead;
-  // with EMB its emb MFMAs) behind the last pair; no branch in the body (loads past the wave's
-  // last tile re-read its last tile, never used)
+  // selection of pair p - 1 behind pair p's MFMAs, tile t + 1's operand (loaded two tiles ahead)
+  // behind the last pair; no branch in the body (loads past the wave's last tile re-read its last
+  // tile, never used)
   for (int t = tb; t < te; ++t) {
     f32x4 acc[kTop1CT];
 #pragma unroll
@@ -818,21 +772,11 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top1_kernel(
         sel(acc[2 * p - 1], 2 * p - 1, t);
       }
     }
-    if constexpr (EMB) {
-      f32x4 e[2];
-      top1_emb_mfma(cv, xn, e);
-      opload(min(t + 2, te - 1), xn);
-      sel(acc[kTop1CT - 2], kTop1CT - 2, t);
-      sel(acc[kTop1CT - 1], kTop1CT - 1, t);
-      top1_emb_norm(t + 1, N1, c16, g, e, a);
-    } else {
-      emb(t + 1, xn, a);
-      opload(min(t + 2, te - 1), xn);
-      sel(acc[kTop1CT - 2], kTop1CT - 2, t);
-      sel(acc[kTop1CT - 1], kTop1CT - 1, t);
-    }
+    unpack(xn, a);
+    opload(min(t + 2, te - 1), xn);
+    sel(acc[kTop1CT - 2], kTop1CT - 2, t);
+    sel(acc[kTop1CT - 1], kTop1CT - 1, t);
   }
-  FD_STAMP(2, __builtin_amdgcn_s_memtime());
   // per column tile: the lane's best (value, row) over its 4 row offsets: the smallest key, then
   // the lowest row holding it
   int bv[kTop1CT];
@@ -858,7 +802,7 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top1_kernel(
         float4 xv[2];
         opload(t, xv);
         float at[8];
-        emb(t, xv, at);
+        unpack(xv, at);
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(at[s], bo[c][s], acc, 0, 0, 0);
@@ -895,7 +839,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top1_kernel(
     for (int c = 0; c < kTop1CT; ++c)
       wkeys[w][c * 16 + c16] = ((unsigned long long)(unsigned)bv[c] << 32) | br[c];
   }
-  FD_STAMP(3, __builtin_amdgcn_s_memtime());
   __syncthreads();
   if (tid < kTop1CT * 16) {
     const int jj = tid, j = j0 + jj;
@@ -912,7 +855,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top1_kernel(
       }
     }
   }
-  FD_STAMP(4, __builtin_amdgcn_s_memtime());
 }
 
 // RS > 1: grid (ceil(V2max / 256), B): the smallest of each column's RS row-part keys (value,
@@ -998,37 +940,6 @@ __device__ __forceinline__ bool t5_any4(bool v) {
   return x != 0;
 }
 
-// the lowest five of this lane's and lane ^ off's ascending 5-lists (unique keys but the ~0
-// padding), ascending, with their slots: the elementwise minimum against the partner's reversed
-// list is a bitonic sequence holding the lowest five, then a 5-input sorting network
-__device__ __forceinline__ void t5_merge_xor(unsigned long long (&bst)[5], int (&bsl)[5], int off) {
-  unsigned long long o[5];
-  int os[5];
-#pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    const unsigned lo = __shfl_xor((unsigned)(bst[q] & 0xffffffffu), off);
-    const unsigned hi = __shfl_xor((unsigned)(bst[q] >> 32), off);
-    o[q] = ((unsigned long long)hi << 32) | lo;
-    os[q] = __shfl_xor(bsl[q], off);
-  }
-#pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    const bool tk = o[4 - q] < bst[q];
-    bst[q] = tk ? o[4 - q] : bst[q];
-    bsl[q] = tk ? os[4 - q] : bsl[q];
-  }
-  auto ce = [&](int x, int y) {
-    const bool sw = bst[y] < bst[x];
-    const unsigned long long kx = bst[x], ky = bst[y];
-    const int sx = bsl[x], sy = bsl[y];
-    bst[x] = sw ? ky : kx;
-    bst[y] = sw ? kx : ky;
-    bsl[x] = sw ? sy : sx;
-    bsl[y] = sw ? sx : sy;
-  };
-  ce(0, 1); ce(3, 4); ce(2, 4); ce(2, 3); ce(0, 3); ce(0, 2); ce(1, 4); ce(1, 3); ce(1, 2);
-}
-
 // a candidate record's (value, row) key
 __device__ __forceinline__ unsigned long long t5_reckey(const u32x4& r) {
   return ((unsigned long long)r[1] << 32) | r[0];
@@ -1041,7 +952,6 @@ __device__ __forceinline__ void ce_i(int& a, int& b) {
   b = hi;
 }
 
-template <int VAR = 0>
 __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
     const f32x4* __restrict__ Atile, int T1, const float* __restrict__ ey, int ldy, const int32_t* __restrict__ n1,
     const int32_t* __restrict__ n2, int V2max, int NCG, int RS, int64_t* __restrict__ out_idx,
@@ -1079,7 +989,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
     }
   }
   const int cg = k % NCG, rs = k / NCG;
-  FD_STAMP(0, __builtin_amdgcn_s_memtime());
   const int j0 = cg * NC;
   const int tid = threadIdx.x, lane = pk::lane_id(), w = __builtin_amdgcn_readfirstlane(pk::wave_id());
   // the column operands' loads go out beside the crop sizes' (as fd_top1_kernel)
@@ -1153,7 +1062,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
         for (int q = 0; q < 4; ++q) bo[c2][4 * h + q] = t4[q];
       }
   }
-  FD_STAMP(1, __builtin_amdgcn_s_memtime());
   int k1[kTop1CT][4], t1[kTop1CT][4], k2[kTop1CT][4];
 #pragma unroll
   for (int c = 0; c < kTop1CT; ++c)
@@ -1212,7 +1120,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
     sel(acc[kTop1CT - 2], kTop1CT - 2, t);
     sel(acc[kTop1CT - 1], kTop1CT - 1, t);
   }
-  FD_STAMP(2, __builtin_amdgcn_s_memtime());
   // E0: the lane minima (over r) of every column, per (wave, lane group)
 #pragma unroll
   for (int c = 0; c < kTop1CT; ++c)
@@ -1245,7 +1152,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
     if (qq == 0) sT[col] = v[4];
   }
   __syncthreads();
-  FD_STAMP(3, __builtin_amdgcn_s_memtime());
   // E2: the candidate streams of each column (minimum <= T). One slot-range reservation per
   // (lane, column) for all of its candidate streams, the 8 reservations in flight together
   {
@@ -1273,7 +1179,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
     }
   }
   __syncthreads();
-  FD_STAMP(4, __builtin_amdgcn_s_memtime());
   // E3: four threads per column (tid = 4 col + qd, lanes of one wave) rank the column's candidates
   // qd, qd + 4, ... against all of them; thread qd then lists the recompute rows of kept stream qd
   // (E3b computes them with every thread of the block, one row each, and keeps those below the
@@ -1319,14 +1224,12 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
       }
     }
   }
-  FD_STAMP(13, __builtin_amdgcn_s_memtime());
   slow = t5_any4(slow);
 #pragma unroll
   for (int q = 0; q < 5; ++q) {
     best[q] = sBest[col][q];
     bsl[q] = sBsl[col][q];
   }
-  FD_STAMP(14, __builtin_amdgcn_s_memtime());
   if (qd == 0) {  // (before the listing below: a full task list flags the column after it)
     sFifth[col] = best[4];
     sXcnt[col] = 0;
@@ -1360,7 +1263,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
     }
   }
   __syncthreads();
-  FD_STAMP(5, __builtin_amdgcn_s_memtime());
   {  // E3b: every listed row's exact distance, one per thread; the few below the column's fifth
      // key go to its short list (any other can never enter the five)
     const int ntask = min(sNtask, kT5Tasks);
@@ -1377,7 +1279,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
     }
   }
   __syncthreads();
-  FD_STAMP(6, __builtin_amdgcn_s_memtime());
   if (qd == 0 && colok) {  // E3c: merge the column's short list
     slow = sXflag[col] != 0;
     if (!slow) {
@@ -1385,8 +1286,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
       for (int x = 0; x < nx; ++x) t5_insert(best, sX[col][x]);
     }
   }
-  FD_STAMP(8, __builtin_amdgcn_s_memtime());
-  FD_STAMP(9, __builtin_amdgcn_s_memtime());
   auto emit = [&](int col, const unsigned long long (&bst)[5]) {
     const int j = j0 + col;
     if (RS == 1) {
@@ -1417,9 +1316,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
   __syncthreads();
   // slow path: one wave per column, every row of this row part, clamped distances, lower row first
   const int nslow = sNslow;
-  FD_STAMP(10, __builtin_amdgcn_s_memtime());
-  FD_STAMP(11, (unsigned long long)nslow);
-  FD_STAMP(12, (unsigned long long)sNtask);
   const int pt0 = (int)((int64_t)nt * (rs * kTop1Waves) / Q), pt1 = (int)((int64_t)nt * (rs * kTop1Waves + kTop1Waves) / Q);
   for (int si = w; si < nslow; si += kTop1Waves) {
     const int col = sSlow[si];
@@ -1445,7 +1341,6 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
     }
     if (lane == 0) emit(col, bl);
   }
-  FD_STAMP(7, __builtin_amdgcn_s_memtime());
 }
 
 struct Top1Plan {
@@ -1453,7 +1348,7 @@ struct Top1Plan {
   int64_t a_bytes, b_bytes, part_bytes;
 };
 
-inline int64_t al256_(int64_t x) { return (x + 255) & ~(int64_t)255; }
+inline int64_t al256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 inline Top1Plan top1_plan(int B, int V1max, int V2max) {
   Top1Plan p{};
@@ -1465,9 +1360,9 @@ inline Top1Plan top1_plan(int B, int V1max, int V2max) {
   p.RS = std::max(1, std::min(rs, T1 / (2 * kTop1Waves)));
   p.T1 = T1;
   p.T2 = T2;
-  p.a_bytes = al256_((int64_t)B * T1 * 2048);
-  p.b_bytes = al256_((int64_t)B * T2 * 2048);
-  p.part_bytes = p.RS > 1 ? al256_((int64_t)B * p.RS * V2max * 8) : 0;
+  p.a_bytes = al256((int64_t)B * T1 * 2048);
+  p.b_bytes = al256((int64_t)B * T2 * 2048);
+  p.part_bytes = p.RS > 1 ? al256((int64_t)B * p.RS * V2max * 8) : 0;
   return p;
 }
 
@@ -1507,8 +1402,6 @@ struct FdPlan {
   int64_t a_bytes, b_bytes, na_bytes, nb_bytes, pv_bytes, pi_bytes;
 };
 
-inline int64_t al256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
 inline FdPlan fd_plan(int B, int V1max, int V2max, int topk, int mode) {
   FdPlan p{};
   p.T1 = (V1max + 15) / 16;
@@ -1538,7 +1431,7 @@ extern "C" int64_t pk_feat_dist_work_size(int B, int V1max, int V2max, int topk,
   // mode 0: the prep + main pass's operand tiles and row-part keys (top-1) / lists (top-5), or the
   // two-pass fallback's scratch (unaligned operand rows); none keeps anything across calls
   const Top1Plan tp = top1_plan(B, V1max, V2max);
-  const int64_t t5parts = tp.RS > 1 ? 2 * al256_((int64_t)B * tp.RS * V2max * 5 * 4) : 0;
+  const int64_t t5parts = tp.RS > 1 ? 2 * al256((int64_t)B * tp.RS * V2max * 5 * 4) : 0;
   return std::max(two_pass, tp.a_bytes + (topk == 1 ? tp.part_bytes : t5parts));
 }
 
@@ -1555,37 +1448,18 @@ extern "C" int pk_feat_dist_topk(const float* evecs_x, int ldx, const float* C, 
   hipStream_t s = pk::as_stream(stream);
   const bool aligned = (ldx % 4) == 0 && (ldy % 4) == 0 && (reinterpret_cast<uintptr_t>(evecs_x) & 15) == 0 &&
                        (reinterpret_cast<uintptr_t>(evecs_y) & 15) == 0;
-#ifdef PK_DEVBUILD
-  static const bool old_top5 = [] {  // development knob PK_FD_TOP5_OLD=1: the round-3 two-pass top-5
-    const char* e = std::getenv("PK_FD_TOP5_OLD");
-    return e && std::atoi(e) == 1;
-  }();
-#else
-  constexpr bool old_top5 = false;
-#endif
-  if (mode == 0 && aligned && V1max > 0 && topk == 5 && !old_top5) {  // prep + main (+ merge when RS > 1)
+  if (mode == 0 && aligned && V1max > 0 && topk == 5) {  // prep + main (+ merge when RS > 1)
     const Top1Plan tp = top1_plan(B, V1max, V2max);
     auto* At = static_cast<f32x4*>(work);
     float* pv = tp.RS > 1 ? reinterpret_cast<float*>(static_cast<char*>(work) + tp.a_bytes) : nullptr;
     int32_t* pi = tp.RS > 1 ? reinterpret_cast<int32_t*>(reinterpret_cast<char*>(pv) +
-                                                         al256_((int64_t)B * tp.RS * V2max * 5 * 4))
+                                                         al256((int64_t)B * tp.RS * V2max * 5 * 4))
                             : nullptr;
     hipLaunchKernelGGL(fd_top1_prep_kernel, dim3((unsigned)(((tp.T1 + 7) / 8) * B)), dim3(512), 0, s, evecs_x, ldx, C,
                        n1, V1max, tp.T1, At, evecs_y, ldy, n2, V2max, (tp.T1 + 7) / 8);
     PK_CHECK_LAUNCH();
-#define PK_FD5(V)                                                                                                \
-  hipLaunchKernelGGL((fd_top5_kernel<V>), dim3((unsigned)((int64_t)B * tp.NCG * tp.RS)), dim3(64 * kTop1Waves), 0, s, \
-                     At, tp.T1, evecs_y, ldy, n1, n2, V2max, tp.NCG, tp.RS, out_idx, out_dist, pv, pi)
-#ifdef PK_DEVBUILD
-    static const int t5var = [] {  // development knob PK_FD_VAR=13: phase stamps (tools/fd_stamps.py)
-      const char* e = std::getenv("PK_FD_VAR");
-      return e ? std::atoi(e) : 0;
-    }();
-    if (t5var == 13) PK_FD5(13); else PK_FD5(0);
-#else
-    PK_FD5(0);
-#endif
-#undef PK_FD5
+    hipLaunchKernelGGL(fd_top5_kernel, dim3((unsigned)((int64_t)B * tp.NCG * tp.RS)), dim3(64 * kTop1Waves), 0, s, At,
+                       tp.T1, evecs_y, ldy, n1, n2, V2max, tp.NCG, tp.RS, out_idx, out_dist, pv, pi);
     PK_CHECK_LAUNCH();
     if (tp.RS > 1) {
       hipLaunchKernelGGL(fd_merge_kernel<5>, dim3((V2max + 255) / 256, B), dim3(256), 0, s, pv, pi, n2, V2max, tp.RS,
@@ -1599,28 +1473,11 @@ extern "C" int pk_feat_dist_topk(const float* evecs_x, int ldx, const float* C, 
     auto* At = static_cast<f32x4*>(work);
     auto* part = reinterpret_cast<unsigned long long*>(static_cast<char*>(work) + tp.a_bytes);
     const dim3 grid((unsigned)((int64_t)B * tp.NCG * tp.RS));
-#ifdef PK_DEVBUILD
-    static const int tvar = [] {  // development knob PK_FD_VAR: 13 phase stamps, 20 emb in the main pass
-      const char* e = std::getenv("PK_FD_VAR");
-      return e ? std::atoi(e) : 0;
-    }();
-#else
-    constexpr int tvar = 0;
-#endif
-    if (tvar != 20) {
-      hipLaunchKernelGGL(fd_top1_prep_kernel, dim3((unsigned)(((tp.T1 + 7) / 8) * B)), dim3(512), 0, s, evecs_x, ldx,
-                         C, n1, V1max, tp.T1, At, evecs_y, ldy, n2, V2max, (tp.T1 + 7) / 8);
-      PK_CHECK_LAUNCH();
-    }
-#define PK_FDT(V, E)                                                                                              \
-  hipLaunchKernelGGL((fd_top1_kernel<V, E>), grid, dim3(64 * kTop1Waves), 0, s, evecs_x, ldx, C, At, tp.T1, evecs_y, \
-                     ldy, n1, n2, V1max, V2max, tp.NCG, tp.RS, out_idx, out_dist, part)
-#ifdef PK_DEVBUILD
-    if (tvar == 13) PK_FDT(13, false); else if (tvar == 20) PK_FDT(0, true); else PK_FDT(0, false);
-#else
-    PK_FDT(0, false);
-#endif
-#undef PK_FDT
+    hipLaunchKernelGGL(fd_top1_prep_kernel, dim3((unsigned)(((tp.T1 + 7) / 8) * B)), dim3(512), 0, s, evecs_x, ldx, C,
+                       n1, V1max, tp.T1, At, evecs_y, ldy, n2, V2max, (tp.T1 + 7) / 8);
+    PK_CHECK_LAUNCH();
+    hipLaunchKernelGGL(fd_top1_kernel, grid, dim3(64 * kTop1Waves), 0, s, evecs_x, ldx, C, At, tp.T1, evecs_y, ldy, n1,
+                       n2, V1max, V2max, tp.NCG, tp.RS, out_idx, out_dist, part);
     PK_CHECK_LAUNCH();
     if (tp.RS > 1) {
       hipLaunchKernelGGL(fd_top1_merge_kernel, dim3((V2max + 255) / 256, B), dim3(256), 0, s, part, n2, V2max, tp.RS,
@@ -1665,11 +1522,3 @@ extern "C" int pk_feat_dist_topk(const float* evecs_x, int ldx, const float* C, 
   }
   return PK_OK;
 }
-
-#ifdef PK_DEVBUILD
-// development: the VAR 13 phase stamps of the last fd_top1_kernel launch (8 per block)
-extern "C" int pkdev_fd_stamps(unsigned long long* host, int n) {
-  if (n > 4096 * 8) n = 4096 * 8;
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fd_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif

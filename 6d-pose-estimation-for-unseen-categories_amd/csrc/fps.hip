@@ -23,8 +23,6 @@
 // repeats, leaving the next centroid in a scalar register.
 #include "common.hpp"
 
-#include <cstdlib>
-
 namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -44,7 +42,10 @@ __device__ __forceinline__ float vmin_f32(float a, float b) {
 
 constexpr int kFpsMaxLds = 13312;  // points whose SoA copy fits in LDS (156 KiB)
 
-template <int NT, int PPT, bool LDS>
+// Plain kernel (crops above the per-lane kernel's 24,576 points): thread t holds the PPT points
+// t + k NT and their running distances in registers, the centroid is read from global memory, and
+// every iteration updates every point.
+template <int NT, int PPT>
 __global__ __launch_bounds__(NT) void fps_kernel(
     const float* __restrict__ xyz, const int64_t* __restrict__ offsets,
     const int32_t* __restrict__ start, const int32_t* __restrict__ npoint,
@@ -61,10 +62,6 @@ __global__ __launch_bounds__(NT) void fps_kernel(
   const float* __restrict__ p = xyz + base * 3;
 
   uint2* slots = reinterpret_cast<uint2*>(smem);  // [2][16] (bits, index)
-  float* sx = reinterpret_cast<float*>(smem + 2 * 16 * sizeof(uint2));
-  const int n_pad = (n + 3) & ~3;
-  float* sy = sx + n_pad;
-  float* sz = sy + n_pad;
 
   float px[PPT], py[PPT], pz[PPT], pd[PPT];
 #pragma unroll
@@ -75,11 +72,6 @@ __global__ __launch_bounds__(NT) void fps_kernel(
       py[k] = p[3 * idx + 1];
       pz[k] = p[3 * idx + 2];
       pd[k] = 1e10f;
-      if (LDS) {
-        sx[idx] = px[k];
-        sy[idx] = py[k];
-        sz[idx] = pz[k];
-      }
     } else {
       px[k] = py[k] = pz[k] = 0.f;
       pd[k] = -1.f;  // empty slot: min(-1, d >= 0) keeps it at -1, never selected
@@ -94,16 +86,9 @@ __global__ __launch_bounds__(NT) void fps_kernel(
   int64_t* __restrict__ o = out + (int64_t)b * out_stride;
   for (int i = 0; i < np; ++i) {
     if (tid == 0) o[i] = far;
-    float cx, cy, cz;
-    if (LDS) {
-      cx = sx[far];
-      cy = sy[far];
-      cz = sz[far];
-    } else {
-      cx = p[3 * far + 0];
-      cy = p[3 * far + 1];
-      cz = p[3 * far + 2];
-    }
+    const float cx = p[3 * far + 0];
+    const float cy = p[3 * far + 1];
+    const float cz = p[3 * far + 2];
     float bd = -1.f;
     int bk = 0;
 #pragma unroll
@@ -134,153 +119,19 @@ __global__ __launch_bounds__(NT) void fps_kernel(
   }
 }
 
-// Pruned variant (the production path). A wave's k-th slot column — indices
-// w*64 + lane + k*NT, 64 consecutive points, a short run of image row in the crop's
-// pixel order — is a bucket with a bounding box and its current max running distance
-// (lane k of the wave holds bucket k's box, max and argmax). Per iteration all buckets of
-// a wave are tested at once (one lane each): if the box lies at computed squared
-// distance lb from the new centroid with lb (1 - 2^-19) >= the bucket max, every point
-// of the bucket has fl(d) >= its running distance (fl(d) >= (1 - 5u) d_true, d_true >=
-// box distance, lb <= (1 + 5u) box distance; 2^-19 > 11u), so fminf leaves it unchanged
-// and the bucket is skipped bit-exactly. Only buckets near the centroid are updated; the
-// wave's best is a reduction over its bucket maxima.
-template <int NT, int PPT>
-__global__ __launch_bounds__(NT) void fps_pruned_kernel(
-    const float* __restrict__ xyz, const int64_t* __restrict__ offsets,
-    const int32_t* __restrict__ start, const int32_t* __restrict__ npoint,
-    int64_t* __restrict__ out, int out_stride) {
-  constexpr int NW = NT / pk::kWave;
-  static_assert(NW <= 16 && PPT <= pk::kWave, "bucket/slot layout limits");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int b = blockIdx.x;
-  const int tid = threadIdx.x;
-  const int lane = pk::lane_id();
-  const int64_t base = offsets[b];
-  const int n = (int)(offsets[b + 1] - base);
-  const int np = npoint[b];
-  const float* __restrict__ p = xyz + base * 3;
-
-  uint2* slots = reinterpret_cast<uint2*>(smem);  // [2][16] (bits, index)
-  float* sx = reinterpret_cast<float*>(smem + 2 * 16 * sizeof(uint2));
-  const int n_pad = (n + 3) & ~3;
-  float* sy = sx + n_pad;
-  float* sz = sy + n_pad;
-
-  float px[PPT], py[PPT], pz[PPT], pd[PPT];
-  // lane k: box of bucket k, its max running distance (as bits) and argmax
-  float bx0 = 0.f, bx1 = 0.f, by0 = 0.f, by1 = 0.f, bz0 = 0.f, bz1 = 0.f;
-  uint32_t bmb = 0u, bmi = 0xffffffffu;
-  bool bval = false;
-  // every point's coordinates first, unconditionally at a clamped index (a conditional load is a
-  // branch + a wait: PPT serial memory round trips before the first iteration)
-  if (n > 0) {  // block-uniform (an empty crop's base may be the end of the buffer)
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-      const int idx = tid + k * NT;
-      const int ic = idx < n ? idx : 0;
-      px[k] = p[3 * ic + 0];
-      py[k] = p[3 * ic + 1];
-      pz[k] = p[3 * ic + 2];
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < PPT; ++k) {
-    const int idx = tid + k * NT;
-    const bool ok = idx < n;
-    if (ok) {
-      pd[k] = 1e10f;
-      sx[idx] = px[k];
-      sy[idx] = py[k];
-      sz[idx] = pz[k];
-    } else {
-      px[k] = py[k] = pz[k] = 0.f;
-      pd[k] = -1.f;  // empty slot: min(-1, d >= 0) keeps it at -1, never selected
-    }
-    const uint64_t any = __ballot(ok);
-    if (any) {  // wave-uniform: bucket k has points
-      const float inf = __builtin_huge_valf();
-      const uint32_t x0 = pk::wave_min_u32_s(pk::f32_ordered(ok ? px[k] : inf));
-      const uint32_t x1 = pk::wave_max_u32_s(pk::f32_ordered(ok ? px[k] : -inf));
-      const uint32_t y0 = pk::wave_min_u32_s(pk::f32_ordered(ok ? py[k] : inf));
-      const uint32_t y1 = pk::wave_max_u32_s(pk::f32_ordered(ok ? py[k] : -inf));
-      const uint32_t z0 = pk::wave_min_u32_s(pk::f32_ordered(ok ? pz[k] : inf));
-      const uint32_t z1 = pk::wave_max_u32_s(pk::f32_ordered(ok ? pz[k] : -inf));
-      if (lane == k) {
-        bx0 = pk::f32_unordered(x0);
-        bx1 = pk::f32_unordered(x1);
-        by0 = pk::f32_unordered(y0);
-        by1 = pk::f32_unordered(y1);
-        bz0 = pk::f32_unordered(z0);
-        bz1 = pk::f32_unordered(z1);
-        bmb = pk::f32_bits(1e10f);
-        bmi = (uint32_t)(pk::wave_id() * pk::kWave + k * NT + (__ffsll((unsigned long long)any) - 1));
-        bval = true;
-      }
-    }
-  }
-  fps_zero_tail(out, out_stride, b, np);
-  if (n <= 0 || np <= 0) return;
-  __syncthreads();
-
-  int far = start[b];
-  int64_t* __restrict__ o = out + (int64_t)b * out_stride;
-  for (int i = 0; i < np; ++i) {
-    if (tid == 0) o[i] = far;
-    const float cx = sx[far], cy = sy[far], cz = sz[far];
-    // one lane per bucket: can the centroid lower any running distance in it?
-    const float ddx = fmaxf(fmaxf(bx0 - cx, cx - bx1), 0.f);
-    const float ddy = fmaxf(fmaxf(by0 - cy, cy - by1), 0.f);
-    const float ddz = fmaxf(fmaxf(bz0 - cz, cz - bz1), 0.f);
-    const float lb = (ddx * ddx + ddy * ddy) + ddz * ddz;
-    const bool need = bval && !(lb * 0.99999809f >= __uint_as_float(bmb));
-    const uint64_t mask = __ballot(need);
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-      if ((mask >> k) & 1ull) {  // wave-uniform (bit k is clear for empty buckets)
-        const float dx = px[k] - cx;
-        const float dy = py[k] - cy;
-        const float dz = pz[k] - cz;
-        const float d = (dx * dx + dy * dy) + dz * dz;  // no contraction (TU flag)
-        pd[k] = fminf(pd[k], d);
-        const bool valid = pd[k] >= 0.f;
-        const uint32_t bits = valid ? pk::f32_bits(pd[k]) : 0u;
-        const uint32_t wmax = pk::wave_max_u32_s(bits);
-        // lanes hold the bucket's indices in increasing order: the first lane at the max
-        // is the lowest index (torch.max's tie rule), no second reduction needed
-        const uint64_t at = __ballot(valid && bits == wmax);
-        const uint32_t widx = (uint32_t)(pk::wave_id() * pk::kWave + k * NT + (__ffsll((unsigned long long)at) - 1));
-        if (lane == k) {
-          bmb = wmax;
-          bmi = widx;
-        }
-      }
-    }
-    // best bucket of the wave: lane k = bucket k and buckets are in increasing index order,
-    // so the first lane at the max holds the lowest index
-    const uint32_t bb = bval ? bmb : 0u;
-    const uint32_t wmax = PPT <= 16 ? pk::readlane(pk::row_max_u32(bb), 0) : pk::wave_max_u32_s(bb);
-    const uint64_t top = __ballot(bval && bb == wmax);
-    const uint32_t widx = top ? pk::readlane(bmi, __ffsll((unsigned long long)top) - 1) : 0xffffffffu;
-    uint2* s = slots + (i & 1) * 16;
-    if (lane == 0) s[pk::wave_id()] = make_uint2(wmax, widx);
-    __syncthreads();
-    uint2 v = make_uint2(0u, 0xffffffffu);
-    if (lane < NW) v = s[lane];
-    const uint32_t m = pk::readlane(pk::row_max_u32(v.x), 0);
-    far = (int)pk::readlane(pk::row_min_u32(v.x == m ? v.y : 0xffffffffu), 0);
-  }
-}
-
-// Per-lane buckets (crops above the LDS bound of fps_pruned_kernel). Thread t holds PPT CONSECUTIVE points
+// Per-lane buckets (crops above the LDS bound of fps_flat_kernel). Thread t holds PPT CONSECUTIVE points
 // (indices t PPT .. t PPT + PPT - 1: a short run of image row in the crop's pixel order, so a
 // compact box), and the lane's running maximum bd is exactly its bucket maximum — tracked
 // anyway for the argmax, so the skip test costs no reduction. A lane updates its points only
-// when the centroid can lower one of them (box distance lb with lb (1 - 2^-19) < bd; the
-// exactness argument of fps_pruned_kernel), and a wave none of whose lanes needs the centroid
-// skips the whole iteration body, reusing its cached (max, index, coordinates). The block
-// result carries the winner's coordinates (no LDS / global read for the next centroid); one
-// barrier per iteration (double-buffered slots). Ties: first maximal index, as torch.max
-// (strict > over a lane's increasing indices; min index among equal maxima across lanes).
+// when the centroid can lower one of them: if the box lies at computed squared distance lb from
+// the new centroid with lb (1 - 2^-19) >= bd, every point of the bucket has fl(d) >= its running
+// distance (fl(d) >= (1 - 5u) d_true, d_true >= box distance, lb <= (1 + 5u) box distance;
+// 2^-19 > 11u), so fminf leaves it unchanged and the bucket is skipped bit-exactly. A wave none
+// of whose lanes needs the centroid skips the whole iteration body, reusing its cached (max,
+// index, coordinates). The block result carries the winner's coordinates (no LDS / global read
+// for the next centroid); one barrier per iteration (double-buffered slots). Ties: first maximal
+// index, as torch.max (strict > over a lane's increasing indices; min index among equal maxima
+// across lanes).
 template <int NT, int PPT>
 __global__ __launch_bounds__(NT) void fps_lane_kernel(
     const float* __restrict__ xyz, const int64_t* __restrict__ offsets,
@@ -406,11 +257,11 @@ __global__ __launch_bounds__(NT) void fps_lane_kernel(
   }
 }
 
-// Flat variant (the production path up to 8192 points). Thread t owns the PPT CONSECUTIVE
+// Flat variant (the production path up to kFpsMaxLds points). Thread t owns the PPT CONSECUTIVE
 // points t PPT .. t PPT + PPT - 1 (so lane order = index order), their running distances and
 // their box; the lane's running maximum bd and its first argmax bk are kept exactly. Per
 // iteration a lane updates its points only when the centroid can lower one of them (box
-// distance lb with lb (1 - 2^-19) < bd, the exactness argument of fps_pruned_kernel), a wave
+// distance lb with lb (1 - 2^-19) < bd, the exactness argument of fps_lane_kernel), a wave
 // whose lanes all skip reuses its cached best, and the block argmax is ONE LDS atomic per wave:
 // ds_max_u64 of key = (distance bits << 32) | ~index (max distance, then lowest index, torch.max's
 // tie rule) into a triple-buffered word, one barrier, one broadcast read. Round 2's kernels spent
@@ -424,20 +275,12 @@ __global__ __launch_bounds__(NT) void fps_lane_kernel(
 // unchanged. (An inline-asm select reading per-compare SGPR masks measured 0.40 but is not kept:
 // hipcc does not pad the VALU-mask-write -> v_cndmask hazard into an asm statement, and it pads
 // two wait states there for its own code.)
-#ifdef PK_DEVBUILD
-// (development: per-wave phase cycle sums of the stamped flat kernel, tools/fps_stamps.py)
-__device__ unsigned long long g_fps_stamps[64 * 16 * 8];
-#endif
-
-template <int NT, int PPT, bool STAMP = false, bool TRIM = true>
+template <int NT, int PPT>
 __global__ __launch_bounds__(NT) void fps_flat_kernel(
     const float* __restrict__ xyz, const int64_t* __restrict__ offsets,
     const int32_t* __restrict__ start, const int32_t* __restrict__ npoint,
     int64_t* __restrict__ out, int out_stride, int prio) {
   pk::set_wave_prio(prio);
-  // STAMP (dev only): per wave, cycles in read + box test / update + wave reduction / atomic +
-  // barrier, and the number of updating iterations
-  [[maybe_unused]] unsigned long long st_box = 0, st_upd = 0, st_bar = 0, st_nupd = 0, t0 = 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [3] (4 words reserved)
   const int b = blockIdx.x;
@@ -496,7 +339,6 @@ __global__ __launch_bounds__(NT) void fps_flat_kernel(
   float cx = sx[far], cy = sy[far], cz = sz[far];
   unsigned long long wkey = 0ull;  // the wave's best (cached while its lanes skip)
   int64_t* __restrict__ o = out + (int64_t)b * out_stride;
-  if (STAMP) t0 = __builtin_amdgcn_s_memtime();
   for (int i = 0; i < np; ++i) {
     if (tid == 0) o[i] = far;
     const float ddx = fmaxf(fmaxf(bx0 - cx, cx - bx1), 0.f);
@@ -505,15 +347,9 @@ __global__ __launch_bounds__(NT) void fps_flat_kernel(
     const float lb = (ddx * ddx + ddy * ddy) + ddz * ddz;
     // an empty lane's bd = -1 fails the test by itself (its box bound is +inf), so the ballot is the
     // bare compare's mask
-    const bool need = TRIM ? !(lb * 0.99999809f >= bd) : lval && !(lb * 0.99999809f >= bd);
+    const bool need = !(lb * 0.99999809f >= bd);
     const uint64_t needm = __ballot(need);
-    unsigned long long t1 = 0;
-    if (STAMP) {
-      t1 = __builtin_amdgcn_s_memtime();
-      st_box += t1 - t0;
-    }
     if (needm) {  // wave-uniform
-      if (STAMP) ++st_nupd;
       if (need) {
         const f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
 #pragma unroll
@@ -531,84 +367,41 @@ __global__ __launch_bounds__(NT) void fps_flat_kernel(
 #pragma unroll
         for (int k = 1; k < PPT; ++k) m = fmaxf(m, D[k >> 1][k & 1]);
         bd = m;
-        if (!TRIM) {  // (development A/B: the round-5 chain, PK_FPS_TRIM=0)
-          int kk = PPT - 1;
-#pragma unroll
-          for (int k = PPT - 2; k >= 0; --k) kk = D[k >> 1][k & 1] == m ? k : kk;
-          bk = kk;
-        }
       }
-      uint32_t wbits, widx;
-      if (!TRIM) {
-        const bool valid = bd >= 0.f;
-        const uint32_t bits = valid ? pk::f32_bits(bd) : 0u;
-        wbits = pk::wave_max_u32_s(bits);
-        const uint64_t at = __ballot(valid && bits == wbits);
-        widx = pk::readlane((uint32_t)(i0 + bk), __ffsll((unsigned long long)at) - 1);
-      } else {
-        // the argmax with the whole wave active (a lane that skipped finds its unchanged bk again),
-        // so the compiler can place its compare -> select wait states under the wave reduction's DPP
-        // chain (plain code: the compiler pads every hazard; an inline-asm select would not be)
-        {
-          int kk = PPT - 1;
+      // the argmax with the whole wave active (a lane that skipped finds its unchanged bk again),
+      // so the compiler can place its compare -> select wait states under the wave reduction's DPP
+      // chain (plain code: the compiler pads every hazard; an inline-asm select would not be)
+      {
+        int kk = PPT - 1;
 #pragma unroll
-          for (int k = PPT - 2; k >= 0; --k) kk = D[k >> 1][k & 1] == bd ? k : kk;  // first k at the max
-          bk = kk;
-        }
-        // signed max of the distance bits: an empty lane's -1.0f is negative and never the max; the
-        // valid lanes are a prefix of the wave, so the first lane at the max is a valid one
-        const int bits = __float_as_int(bd);
-        wbits = (uint32_t)pk::wave_max_i32_s(bits);
-        const uint64_t at = __builtin_amdgcn_uicmp((uint32_t)bits, wbits, 32 /* EQ */);
-        widx = pk::readlane((uint32_t)(i0 + bk), __ffsll((unsigned long long)at) - 1);
+        for (int k = PPT - 2; k >= 0; --k) kk = D[k >> 1][k & 1] == bd ? k : kk;  // first k at the max
+        bk = kk;
       }
+      // signed max of the distance bits: an empty lane's -1.0f is negative and never the max; the
+      // valid lanes are a prefix of the wave, so the first lane at the max is a valid one
+      const int bits = __float_as_int(bd);
+      const uint32_t wbits = (uint32_t)pk::wave_max_i32_s(bits);
+      const uint64_t at = __builtin_amdgcn_uicmp((uint32_t)bits, wbits, 32 /* EQ */);
+      const uint32_t widx = pk::readlane((uint32_t)(i0 + bk), __ffsll((unsigned long long)at) - 1);
       wkey = ((unsigned long long)wbits << 32) | (unsigned long long)(0xffffffffu - widx);
-    }
-    unsigned long long t2 = 0;
-    if (STAMP) {
-      t2 = __builtin_amdgcn_s_memtime();
-      st_upd += t2 - t1;
     }
     if (lane == 0 && wkey != 0ull) atomicMax(&keys[i % 3], wkey);
     if (tid == 0) keys[(i + 1) % 3] = 0ull;  // last read after barrier i - 2: every wave is past it
     __syncthreads();
-    if (STAMP) {
-      t0 = __builtin_amdgcn_s_memtime();
-      st_bar += t0 - t2;
-    }
     const unsigned long long key = keys[i % 3];
     far = (int)(0xffffffffu - (uint32_t)(key & 0xffffffffull));
     cx = sx[far];
     cy = sy[far];
     cz = sz[far];
   }
-#ifdef PK_DEVBUILD
-  if (STAMP && lane == 0 && b < 64) {
-    unsigned long long* g = g_fps_stamps + ((size_t)b * 16 + pk::wave_id()) * 8;
-    g[0] = st_box;
-    g[1] = st_upd;
-    g[2] = st_bar;
-    g[3] = st_nupd;
-    g[4] = (unsigned long long)np;
-  }
-#endif
 }
 
-template <int NT, int PPT, bool STAMP = false>
+template <int NT, int PPT>
 int launch_fps_flat(const float* xyz, const int64_t* offsets, const int32_t* start, const int32_t* npoint,
                     int64_t* out, int out_stride, int B, int nmax, hipStream_t s) {
   const int n_pad = (nmax + 3) & ~3;
   const size_t lds = 4 * sizeof(unsigned long long) + 3 * (size_t)n_pad * sizeof(float);
-#ifdef PK_DEVBUILD
-  static const bool untrimmed = getenv("PK_FPS_TRIM") && atoi(getenv("PK_FPS_TRIM")) == 0;
-  if (untrimmed) {
-    hipLaunchKernelGGL((fps_flat_kernel<NT, PPT, STAMP, false>), dim3(B), dim3(NT), lds, s, xyz, offsets, start,
-                       npoint, out, out_stride, pk::side_prio());
-    PK_CHECK_LAUNCH();
-    return PK_OK;
-  }
-#endif
-  hipLaunchKernelGGL((fps_flat_kernel<NT, PPT, STAMP>), dim3(B), dim3(NT), lds, s, xyz, offsets, start, npoint, out,
+  hipLaunchKernelGGL((fps_flat_kernel<NT, PPT>), dim3(B), dim3(NT), lds, s, xyz, offsets, start, npoint, out,
                      out_stride, pk::side_prio());
   PK_CHECK_LAUNCH();
   return PK_OK;
@@ -623,37 +416,27 @@ int launch_fps_lane(const float* xyz, const int64_t* offsets, const int32_t* sta
   return PK_OK;
 }
 
-template <int NT, int PPT>
-int launch_fps(const float* xyz, const int64_t* offsets, const int32_t* start,
-               const int32_t* npoint, int64_t* out, int out_stride, int B, int nmax,
-               hipStream_t s) {
-  const size_t slots = 2 * 16 * sizeof(uint2);
-  if (nmax <= kFpsMaxLds) {
-    const int n_pad = (nmax + 3) & ~3;
-    const size_t lds = slots + 3 * (size_t)n_pad * sizeof(float);
-    hipLaunchKernelGGL((fps_pruned_kernel<NT, PPT>), dim3(B), dim3(NT), lds, s, xyz, offsets,
-                       start, npoint, out, out_stride);
-  } else {
-    hipLaunchKernelGGL((fps_kernel<NT, PPT, false>), dim3(B), dim3(NT), slots, s, xyz, offsets,
-                       start, npoint, out, out_stride);
-  }
-  PK_CHECK_LAUNCH();
-  return PK_OK;
+// flat kernel (one LDS atomic per wave per iteration) up to the LDS bound (3 x 13312 floats + the
+// key words = 156 KiB)
+int fps_flat(const float* xyz, const int64_t* offsets, const int32_t* start, const int32_t* npoint, int64_t* out,
+             int out_stride, int B, int nmax, hipStream_t s) {
+  if (nmax <= 1024) return launch_fps_flat<1024, 1>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
+  if (nmax <= 2048) return launch_fps_flat<1024, 2>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
+  if (nmax <= 4096) return launch_fps_flat<1024, 4>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
+  if (nmax <= 8192) return launch_fps_flat<1024, 8>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
+  // 10 points per lane up to 10,240 (the bench's synthetic frames: up to 9,289 mask pixels): an
+  // updating wave's distance / argmax work scales with the points per lane
+  if (nmax <= 10240) return launch_fps_flat<1024, 10>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
+  if (nmax <= kFpsMaxLds) return launch_fps_flat<1024, 13>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
+  return PK_ERR_ARG;
 }
 
-// The unpruned kernel at a forced configuration (dev comparisons).
-template <int NT, int PPT>
-int launch_fps_plain(const float* xyz, const int64_t* offsets, const int32_t* start,
-                     const int32_t* npoint, int64_t* out, int out_stride, int B, int nmax,
-                     hipStream_t s) {
-  const size_t slots = 2 * 16 * sizeof(uint2);
-  const int n_pad = (nmax + 3) & ~3;
-  const size_t lds = slots + 3 * (size_t)n_pad * sizeof(float);
-  if (nmax > kFpsMaxLds) return PK_ERR_ARG;
-  hipLaunchKernelGGL((fps_kernel<NT, PPT, true>), dim3(B), dim3(NT), lds, s, xyz, offsets, start,
-                     npoint, out, out_stride);
-  PK_CHECK_LAUNCH();
-  return PK_OK;
+// per-lane buckets, points in registers only (no LDS copy of the crop)
+int fps_lane(const float* xyz, const int64_t* offsets, const int32_t* start, const int32_t* npoint, int64_t* out,
+             int out_stride, int B, int nmax, hipStream_t s) {
+  if (nmax <= 16384) return launch_fps_lane<1024, 16>(xyz, offsets, start, npoint, out, out_stride, B, s);
+  if (nmax <= 24576) return launch_fps_lane<1024, 24>(xyz, offsets, start, npoint, out, out_stride, B, s);
+  return PK_ERR_ARG;
 }
 
 }  // namespace
@@ -675,73 +458,25 @@ extern "C" int pk_fps(const float* xyz, const int64_t* offsets, int B, int nmax,
       if (rc != PK_OK) return rc;
     }
   }
-#ifndef PK_FPS_ROUND2  // flat kernel (one LDS atomic per wave per iteration) up to 8192 points
-  if (nmax <= 1024) return launch_fps_flat<1024, 1>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
-  if (nmax <= 2048) return launch_fps_flat<1024, 2>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
-  if (nmax <= 4096) return launch_fps_flat<1024, 4>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
-  if (nmax <= 8192) return launch_fps_flat<1024, 8>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
-  // up to the LDS bound (3 x 13312 floats + the key words = 156 KiB): the bench's 640x480 crops
-  // (8-9k points) ran the pruned kernel at 0.78 us per iteration; the flat one measured 0.53 at 1024 threads
-  // 10 points per lane up to 10,240 (the bench's synthetic frames: up to 9,289 mask pixels): an
-  // updating wave's distance / argmax work scales with the points per lane
-  if (nmax <= 10240) return launch_fps_flat<1024, 10>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
-  if (nmax <= kFpsMaxLds) return launch_fps_flat<1024, 13>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
-#endif
-#define PK_FPS(NT, PPT) return launch_fps<NT, PPT>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s)
-#ifdef PK_DEVBUILD
-  // development knob (read once): PK_FPS_NT=256 / 512 runs the pruned kernel with fewer waves per
-  // crop above 4096 points (less of each CU held while crop formation overlaps the step)
-  static const int fps_nt = getenv("PK_FPS_NT") ? atoi(getenv("PK_FPS_NT")) : 1024;
-  if (nmax > 4096 && nmax <= 8192 && fps_nt == 512) PK_FPS(512, 16);
-  if (nmax > 4096 && nmax <= 13312 && fps_nt == 512) PK_FPS(512, 26);
-  if (nmax > 4096 && nmax <= 8192 && fps_nt == 256) PK_FPS(256, 32);
-  if (nmax > 4096 && nmax <= 13312 && fps_nt == 256) PK_FPS(256, 52);
-#endif
-  // 1024-thread workgroups above 4096 points: measured 0.712 us per FPS step against 0.78
-  // (512 threads) and 1.09 (256) on the bench's crops (n <= 6588, profiles/r02_kbench_fps.txt)
-  if (nmax <= 1024) PK_FPS(256, 4);
-  if (nmax <= 2048) PK_FPS(256, 8);
-  if (nmax <= 4096) PK_FPS(256, 16);
-#ifdef PK_FPS_LANE_ABOVE_4096  // development variant: per-lane buckets (no LDS point copy) above 4096
-  if (nmax <= 8192) return launch_fps_lane<1024, 8>(xyz, offsets, start, npoint, out, out_stride, B, s);
-  if (nmax <= 13312) return launch_fps_lane<1024, 13>(xyz, offsets, start, npoint, out, out_stride, B, s);
-#endif
-  if (nmax <= 8192) PK_FPS(1024, 8);
-  if (nmax <= 13312) PK_FPS(1024, 13);
-#undef PK_FPS
-  // beyond the LDS copy of the pruned kernel: per-lane buckets, points in registers only
-  if (nmax <= 16384) return launch_fps_lane<1024, 16>(xyz, offsets, start, npoint, out, out_stride, B, s);
-  if (nmax <= 24576) return launch_fps_lane<1024, 24>(xyz, offsets, start, npoint, out, out_stride, B, s);
-  if (nmax <= 32768) return launch_fps<1024, 32>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
-  return PK_ERR_ARG;  // > 32768 points per crop
+  if (nmax <= kFpsMaxLds) return fps_flat(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
+  if (nmax <= 24576) return fps_lane(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
+  if (nmax > 32768) return PK_ERR_ARG;  // > 32768 points per crop
+  hipLaunchKernelGGL((fps_kernel<1024, 32>), dim3(B), dim3(1024), 2 * 16 * sizeof(uint2), s, xyz, offsets, start,
+                     npoint, out, out_stride);
+  PK_CHECK_LAUNCH();
+  return PK_OK;
 }
 
 #ifdef PK_DEVBUILD
-// Development hook (not part of include/posekern.h): force the block size / points
-// per thread, flat with phase stamps (pruned = 6), flat (4), per-lane buckets (3), pruned (1) or plain (0), for tools/kbench.py's sweeps.
+// Development hook (not part of include/posekern.h): force the flat (mode 4) or the per-lane
+// (mode 3) kernel whatever the crop size, for tools/kbench.py's comparison.
 extern "C" int pkdev_fps_cfg(const float* xyz, const int64_t* offsets, int B, int nmax,
                              const int32_t* start, const int32_t* npoint, int64_t* out,
-                             int out_stride, int nt, int pruned, void* stream) {
+                             int out_stride, int nt, int mode, void* stream) {
   hipStream_t s = pk::as_stream(stream);
-  const int ppt = (nmax + nt - 1) / nt;
-#define PK_FPS(NT, PPT)                                                                          \
-  if (nt == NT && ppt <= PPT)                                                                    \
-    return pruned == 6 ? launch_fps_flat<NT, PPT, true>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s) \
-           : pruned == 4 ? launch_fps_flat<NT, PPT>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s) \
-           : pruned == 3 ? launch_fps_lane<NT, PPT>(xyz, offsets, start, npoint, out, out_stride, B, s) \
-           : pruned ? launch_fps<NT, PPT>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s) \
-                  : launch_fps_plain<NT, PPT>(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
-  PK_FPS(256, 4) PK_FPS(256, 8) PK_FPS(256, 16) PK_FPS(256, 32)
-  PK_FPS(512, 2) PK_FPS(512, 4) PK_FPS(512, 8) PK_FPS(512, 16) PK_FPS(512, 26)
-  PK_FPS(1024, 2) PK_FPS(1024, 4) PK_FPS(1024, 8) PK_FPS(1024, 10) PK_FPS(1024, 13)
-#undef PK_FPS
+  if (nt != 1024) return PK_ERR_ARG;
+  if (mode == 4) return fps_flat(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
+  if (mode == 3) return fps_lane(xyz, offsets, start, npoint, out, out_stride, B, nmax, s);
   return PK_ERR_ARG;
-}
-#endif  // PK_DEVBUILD
-
-#ifdef PK_DEVBUILD
-extern "C" int pkdev_fps_stamps(unsigned long long* host, int n) {
-  if (n > 64 * 16 * 8) n = 64 * 16 * 8;
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fps_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
 }
 #endif  // PK_DEVBUILD

@@ -13,18 +13,14 @@
 #include "mfma_tile.hpp"
 #include "../../include/posekern.h"
 
-#include <cstdlib>
+#include <algorithm>
 
 using namespace pk;  // the tile helpers of mfma_tile.hpp
 
 namespace {
 
 constexpr int kLfMaxC = 128;
-// rows kernel grid cap (development knob PK_ROWS_BLOCKS at build time; 4 waves per block)
-#ifndef PK_ROWS_BLOCKS
-#define PK_ROWS_BLOCKS 4096
-#endif
-constexpr int kRowsMaxBlocks = PK_ROWS_BLOCKS;
+constexpr int kRowsMaxBlocks = 4096;  // rows kernel grid cap (4 waves per block)
 
 // ReLU backward folded into an input-gradient epilogue: mask = the forward output of the layer
 // whose gradient this is (aten threshold_backward(grad, mask, 0): mask <= 0 -> 0)
@@ -61,24 +57,6 @@ struct LinEpi {
 
 __device__ __forceinline__ float lin_act(int act, float v) {
   return act == 1 ? fmaxf(v, 0.f) : act == 2 ? 1.f / (1.f + expf(-v)) : v;
-}
-
-__device__ __forceinline__ float lin_epi(const LinEpi& e, float v, int64_t mask_i) {
-  return relu_mask(lin_act(e.relu, v), e.mask, mask_i);
-}
-
-// rows-layout store of output column o of point r (Cout outputs per point)
-__device__ __forceinline__ void lin_store_row(const LinEpi& e, int64_t r, int o, int Cout, float v) {
-  v = lin_epi(e, v, r * Cout + o);
-  if (e.add != nullptr && o < e.add_cols) v += e.add[r * e.sa + o];
-  if (e.store_cf) {
-    const int64_t b = r / e.N, n = r - b * e.N;
-    e.y[b * e.sy + (int64_t)o * e.N + n] = v;
-  } else if (o >= e.split) {
-    e.y2[r * e.sy2 + (o - e.split)] = v;
-  } else {
-    e.y[r * e.sy + o] = v;
-  }
 }
 
 template <int LAYOUT>
@@ -791,21 +769,10 @@ static int lin_setup(const pk_linear_args* a, LinEpi& e, int64_t& sx_out) {
 
 // points per wave of the channels-first kernel: 16 SUB, as many as keep >= 1024 waves and <= 64
 // operand VGPRs; SUB-aligned items and strides for the vector loads / stores
-// development knob PK_CF_SUBMAX (1, 2, 4): cap on the channels-first points-per-lane choice
-static int cf_submax() {
-#ifdef PK_DEVBUILD
-  static const int v = [] { const char* e = std::getenv("PK_CF_SUBMAX"); return e ? std::atoi(e) : 4; }();
-  return v;
-#else
-  return 4;
-#endif
-}
-
 static int cf_sub(int64_t R, int N, int Cin, int64_t sx, const LinEpi& e) {
   // 16 points per wave below 131,072 rows (round 6: the configs[1] step's 65,536-row layers ran
-  // 11 % faster than with 32 — more waves in flight per CU; tools/cf_sub_ab.sh)
+  // 11 % faster than with 32 — more waves in flight per CU)
   int sub = R >= 131072 ? 4 : 1;
-  sub = std::min(sub, cf_submax());
   sub = std::min(sub, 256 / Cin);
   while (sub > 1 && N % (16 * sub)) sub >>= 1;  // N % 16 != 0: SUB = 1 with ragged item tails
   while (sub > 1 && ((sx % sub) || (e.sy % sub) || (e.add && (e.sa % sub)) || (e.add2 && (e.sa2 % sub)))) sub >>= 1;
@@ -910,12 +877,7 @@ extern "C" int pk_linear_ex(const pk_linear_args* a, void* stream) {
     };
     // plain: no mask, no residual add, one contiguous output (split == Cout)
     const bool plain = e.mask == nullptr && e.add == nullptr && e.y2 == nullptr && !e.store_cf && e.split >= Cout;
-#ifdef PK_DEVBUILD
-    static const bool glds_on = getenv("PK_ROWS_GLDS") == nullptr || atoi(getenv("PK_ROWS_GLDS")) != 0;
-#else
-    constexpr bool glds_on = true;
-#endif
-    const bool glds_ok = glds_on && Cin >= 32 && Cout >= 32 && Cout % 16 == 0 && TO * (Cin / 16) <= 32 &&
+    const bool glds_ok = Cin >= 32 && Cout >= 32 && Cout % 16 == 0 && TO * (Cin / 16) <= 32 &&
                          e.relu <= 1 && !e.store_cf && al16(x) && al16(e.y) && e.sy % 4 == 0 &&
                          (e.y2 == nullptr || (al16(e.y2) && e.sy2 % 4 == 0 && e.split % 16 == 0)) &&
                          (e.mask == nullptr || al16(e.mask)) && (e.add == nullptr || (al16(e.add) && e.sa % 4 == 0));

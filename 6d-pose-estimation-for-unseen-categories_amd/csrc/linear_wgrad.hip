@@ -4,116 +4,25 @@
 //     dW[o, i] = sum_r dY[r, o] X[r, i],   db[o] = sum_r dY[r, o]
 // over every point of every crop (r = B * N rows, 32768-65536 per call) into a tiny
 // [O <= 128, I <= 128] result. A library GEMM tiles the output (a handful of tiles) and
-// walks all rows serially; here the rows are split into 128-row slices, one workgroup per
-// slice, each contracting its slice on the f32 MFMA (v_mfma_f32_16x16x4f32: exact f32
-// products, f32 accumulation) into a partial [O, I]; a second pass sums the partials in
-// slice order (deterministic).
+// walks all rows serially; here the rows are split into slices of at least 128 rows, one
+// workgroup per slice, each contracting its slice on the f32 MFMA (exact f32 products, f32
+// accumulation) into a partial [O, I]; a second pass sums the partials in slice order
+// (deterministic).
 //
 // Layouts: 0 = rows x channels ([R, C] row-major, nn.Linear), 1 = channels-first
 // ([Bn, C, N], Conv1d with kernel 1; row r = (r / N, r % N)).
 #include "mfma_tile.hpp"
 #include "../../include/posekern.h"
 
-#include <cstdlib>
 #include <vector>
 
 using namespace pk;  // the tile helpers of mfma_tile.hpp
 
 namespace {
 
-constexpr int kChunk = 32;          // rows staged per step (8 MFMA k-steps)
-constexpr int kSlice = 128;         // rows per workgroup
+constexpr int kSlice = 128;         // least rows per workgroup
 constexpr int kMaxC = 128;          // I, O <= 128
-constexpr int kStride = kMaxC + 16; // LDS row stride (mod 64 = 16: conflict-free A/B reads)
 constexpr int kMaxTilesPerWave = 8;  // O * I <= 128 * 64
-
-__device__ __forceinline__ float load_rc(const float* __restrict__ p, int layout, int C, int N, int64_t r,
-                                         int c) {
-  if (layout == 0) return p[r * C + c];
-  const int64_t b = r / N, n = r - b * N;
-  return p[(b * C + c) * N + n];
-}
-
-// Stage rows [r0, r0 + kChunk) of a [R, C] operand into s[row][c] (zero padded). All
-// global loads of the chunk are issued before the first LDS store (one wait per chunk).
-__device__ __forceinline__ void stage_rows(const float* __restrict__ p, int layout, int C, int N, int64_t R,
-                                           int64_t r0, float* __restrict__ s) {
-  const int cp = (C + 15) & ~15;
-  const int total = kChunk * cp;
-  constexpr int kPer = kChunk * kMaxC / 256;
-  float v[kPer];
-#pragma unroll
-  for (int q = 0; q < kPer; ++q) {
-    const int e = threadIdx.x + q * 256;
-    const int row = layout == 0 ? e / cp : e % kChunk;  // channels-first: threads walk rows
-    const int c = layout == 0 ? e % cp : e / kChunk;    // (contiguous in memory)
-    const int64_t r = r0 + row;
-    v[q] = (e < total && c < C && r < R) ? load_rc(p, layout, C, N, r, c) : 0.f;
-  }
-#pragma unroll
-  for (int q = 0; q < kPer; ++q) {
-    const int e = threadIdx.x + q * 256;
-    const int row = layout == 0 ? e / cp : e % kChunk;
-    const int c = layout == 0 ? e % cp : e / kChunk;
-    if (e < total) s[row * kStride + c] = v[q];
-  }
-}
-
-__global__ __launch_bounds__(256) void wgrad_partial_kernel(const float* __restrict__ x,
-                                                            const float* __restrict__ dy, int layout,
-                                                            int64_t R, int I, int O, int N,
-                                                            float* __restrict__ part,
-                                                            float* __restrict__ partb) {
-  __shared__ float Xs[kChunk * kStride];
-  __shared__ float Ys[kChunk * kStride];
-  const int s = blockIdx.x;
-  const int lane = pk::lane_id(), g = lane >> 4, c = lane & 15, w = pk::wave_id();
-  const int It = (I + 15) >> 4, Ot = (O + 15) >> 4, T = It * Ot;
-  f32x4 acc[kMaxTilesPerWave];
-#pragma unroll
-  for (int j = 0; j < kMaxTilesPerWave; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float bacc = 0.f;
-  const int64_t r_begin = (int64_t)s * kSlice;
-  const int64_t r_end = r_begin + kSlice < R ? r_begin + kSlice : R;
-  for (int64_t r0 = r_begin; r0 < r_end; r0 += kChunk) {
-    __syncthreads();
-    stage_rows(x, layout, I, N, r_end, r0, Xs);
-    stage_rows(dy, layout, O, N, r_end, r0, Ys);
-    __syncthreads();
-    if (threadIdx.x < O) {
-#pragma unroll 8
-      for (int r = 0; r < kChunk; ++r) bacc += Ys[r * kStride + threadIdx.x];
-    }
-#pragma unroll
-    for (int j = 0; j < kMaxTilesPerWave; ++j) {
-      const int t = w + 4 * j;
-      if (t < T) {
-        const int to = t / It, ti = t - to * It;
-#pragma unroll
-        for (int k = 0; k < kChunk / 4; ++k) {
-          const float a = Ys[(4 * k + g) * kStride + to * 16 + c];  // dY^T [o][r]
-          const float b = Xs[(4 * k + g) * kStride + ti * 16 + c];  // X [r][i]
-          acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[j], 0, 0, 0);
-        }
-      }
-    }
-  }
-  float* __restrict__ ps = part + (int64_t)s * O * I;
-#pragma unroll
-  for (int j = 0; j < kMaxTilesPerWave; ++j) {
-    const int t = w + 4 * j;
-    if (t < T) {
-      const int to = t / It, ti = t - to * It;
-      const int i = ti * 16 + c;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int o = to * 16 + 4 * g + rr;
-        if (o < O && i < I) ps[o * I + i] = acc[j][rr];
-      }
-    }
-  }
-  if (threadIdx.x < O) partb[(int64_t)s * O + threadIdx.x] = bacc;
-}
 
 // dw[e] = sum_s part[s, e] (e < O*I), db[o] = sum_s partb[s, o]. Block = 64 outputs x
 // 16 slice groups (two interleaved chains each), combined by a fixed pairwise tree:
@@ -350,7 +259,7 @@ struct WgradProblem {
   const float* dy;
   float* part;   // S * O * I weight partials, then S * O bias partials
   int64_t R;
-  int I, O, N, layout, SL, S, blk0, pad;  // pad: the pipeline kernel's development variant (0)
+  int I, O, N, layout, SL, S, blk0, pad;  // pad: unused (0); keeps the 8-byte members aligned
   int64_t sbx, sbdy;  // channels-first batch strides (0: dense)
 };
 struct WgradProblems {
@@ -556,7 +465,6 @@ __device__ __forceinline__ void wgrad_glds_body(const WgradProblem& P, int s, fl
     for (int64_t k = 0; k < nt; ++k) {
       issue(k + kWgD - 1);
       vm_wait<(kWgD - 1) * G>();  // tile k landed (glds retire in issue order)
-      if (P.pad == 2) continue;  // (development variant: the glds stream alone)
       const float* sx = ring + (k % kWgD) * SLOT;
       const float* sd = sx + XS;
       if constexpr (LAYOUT == 0) {
@@ -576,10 +484,6 @@ __device__ __forceinline__ void wgrad_glds_body(const WgradProblem& P, int s, fl
           }
 #pragma unroll
           for (int t = 0; t < TO; ++t) bs[t] += a[t];
-          if (P.pad == 1) {  // (development variant: the operand stream without the MFMAs)
-            acc[0][0][0] += b[0];
-            continue;
-          }
 #pragma unroll
           for (int t = 0; t < TO; ++t)
 #pragma unroll
@@ -597,10 +501,6 @@ __device__ __forceinline__ void wgrad_glds_body(const WgradProblem& P, int s, fl
         for (int u = 0; u < TI; ++u) {
           const int c = m + 16 * u;
           b[u] = *reinterpret_cast<const f32x4*>(sx + 16 * c + 4 * (g ^ ((c >> 2) & 3)));
-        }
-        if (P.pad == 1) {  // (development variant: the operand stream without the MFMAs)
-          acc[0][0] += b[0];
-          continue;
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -706,25 +606,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_glds_grouped_kernel(const WgradP
 
 }  // namespace
 
-#ifdef PK_DEVBUILD
-// Development hook (not in include/posekern.h): the LDS-staged slice kernel, for A/B timing.
-extern "C" int pkdev_linear_wgrad_v1(const float* x, const float* dy, int layout, int64_t R, int I, int O, int N,
-                                     float* work, float* dw, float* db, void* stream) {
-  hipStream_t s = pk::as_stream(stream);
-  const int S = (int)((R + kSlice - 1) / kSlice);
-  if (S == 0) return PK_ERR_ARG;
-  float* part = work;
-  float* partb = work + (int64_t)S * O * I;
-  hipLaunchKernelGGL(wgrad_partial_kernel, dim3(S), dim3(256), 0, s, x, dy, layout, R, I, O, N, part, partb);
-  PK_CHECK_LAUNCH();
-  const int total = O * I + O;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((total + 63) / 64), dim3(64 * kRedGroups), 0, s, part, partb, S, O * I, O,
-                     dw, db, 0);
-  PK_CHECK_LAUNCH();
-  return PK_OK;
-}
-#endif  // PK_DEVBUILD
-
 extern "C" int pk_linear_wgrad(const float* x, const float* dy, int layout, int64_t R, int I, int O, int N,
                                float* work, float* dw, float* db, int accumulate, void* stream) {
   PK_REQUIRE((layout == 0 || layout == 1) && R >= 0 && I > 0 && O > 0 && I <= kMaxC && O <= kMaxC);
@@ -768,21 +649,7 @@ extern "C" int pk_linear_wgrad(const float* x, const float* dy, int layout, int6
 // wg_shape_id, channels-first only with N % 16 == 0, 16-B aligned operands) get blocks in
 // proportion to their cost (wg_cost), about kWgBlocks in all (slices of whole 16-row tiles, >= 64
 // rows); the others keep round 3's wgrad_v2 slicing. S[c] partials of call c, SL[c] rows each.
-// development variants of the pipeline kernel (limiter study): 1 no MFMAs, 2 no LDS reads either
-static int wg_variant() {
-#ifdef PK_DEVBUILD
-  static const int v = getenv("PK_WG_VAR") ? atoi(getenv("PK_WG_VAR")) : 0;
-  return v;
-#else
-  return 0;
-#endif
-}
-
 static bool wg_on_pipeline(const pk_wgrad_call& k) {
-#ifdef PK_DEVBUILD
-  static const bool on = getenv("PK_WG_GLDS") == nullptr || atoi(getenv("PK_WG_GLDS")) != 0;
-  if (!on) return false;
-#endif
   return k.R > 0 && wg_shape_id(k.I, k.O, k.layout) >= 0 && (k.layout == 0 || k.N % 16 == 0) &&
          ((reinterpret_cast<uintptr_t>(k.x) | reinterpret_cast<uintptr_t>(k.dy)) & 15) == 0;
 }
@@ -806,9 +673,6 @@ static int wg_budget() {
                                                  hipSuccess || n <= 0)
       n = kWgBlocks / 4;
     n *= 4;
-#ifdef PK_DEVBUILD
-    if (const char* e = getenv("PK_WG_BUDGET")) n = atoi(e) > 0 ? atoi(e) : n;  // (development knob)
-#endif
     return n;
   }();
   return cus;
@@ -935,7 +799,7 @@ extern "C" int pk_linear_wgrad_grouped(const pk_wgrad_call* calls, int n, float*
       if (S[c] == 0 || !glds[c]) continue;
       WgradProblem& P = tp.p[tp.G++];
       P = WgradProblem{k.x, k.dy, work + off[c], k.R, k.I, k.O, k.N, k.layout, (int)SLv[c], (int)S[c], blocks,
-                       wg_variant(), k.sx, k.sdy};
+                       0, k.sx, k.sdy};
       blocks += (int)S[c];
       if (tp.G == kGroupMax) {
         const int rc = flush();

@@ -14,213 +14,12 @@
 
 namespace {
 
-constexpr int kRows = 64;     // rows of Phi reduced per block in pass 1
-constexpr int kSub = 32;      // rows staged in LDS per step
+constexpr int kRows = 64;     // rows of Phi per chunk of pass 1
 constexpr int kKC = 64;       // K == C == 64 (C_width, k_eig) — checked on the host
 
-// pass 1: part[b, s] = sum_{rows in chunk s} Phi[r, :]^T (w_r * x[r, :]), w = mass or 1.
-// grid (S, B), block 256 = 16 x 16 threads, each owning a 4 x 4 output micro-tile.
-__global__ __launch_bounds__(256) void spec_reduce_kernel(const float* __restrict__ x, int ldx,
-                                                          const float* __restrict__ mass,
-                                                          const float* __restrict__ evecs, int N, int S,
-                                                          float* __restrict__ part) {
-  __shared__ float4 sphi[kSub][kKC / 4 + 1];
-  __shared__ float4 sx[kSub][kKC / 4 + 1];
-  const int s = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int ty = tid >> 4, tx = tid & 15;
-  const float* __restrict__ phi = evecs + (int64_t)b * N * kKC;
-  const float* __restrict__ xb = x + (int64_t)b * N * ldx;
-  const float* __restrict__ mb = mass ? mass + (int64_t)b * N : nullptr;
-  float acc[4][4] = {};
-  const int r_begin = s * kRows;
-  const int r_end = min(N, r_begin + kRows);
-  for (int r0 = r_begin; r0 < r_end; r0 += kSub) {
-    __syncthreads();
-    for (int e = tid; e < kSub * (kKC / 4); e += 256) {
-      const int rr = e / (kKC / 4), q = e % (kKC / 4);
-      const int r = r0 + rr;
-      float4 pv = make_float4(0.f, 0.f, 0.f, 0.f), xv = pv;
-      if (r < r_end) {
-        pv = reinterpret_cast<const float4*>(phi + (int64_t)r * kKC)[q];
-        xv = reinterpret_cast<const float4*>(xb + (int64_t)r * ldx)[q];
-        if (mb) {
-          const float w = mb[r];
-          xv.x *= w; xv.y *= w; xv.z *= w; xv.w *= w;
-        }
-      }
-      sphi[rr][q] = pv;
-      sx[rr][q] = xv;
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int rr = 0; rr < kSub; ++rr) {
-      const float4 p = sphi[rr][ty];
-      const float4 v = sx[rr][tx];
-      const float pk[4] = {p.x, p.y, p.z, p.w};
-      const float vc[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(pk[i], vc[j], acc[i][j]);
-    }
-  }
-  float* __restrict__ o = part + ((int64_t)b * S + s) * kKC * kKC;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    reinterpret_cast<float4*>(o + (ty * 4 + i) * kKC)[tx] = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
-}
-
-// pass 2: coef = sum_s part; save raw (optional), scaled = E ⊙ coef; optional gt partial
-// gt[b, c] = -sum_k lambda_k E[k,c] saved[k,c] coef[k,c]. grid (B), block 1024: thread
-// (k-quad, c) sums its 4 rows over the S partials as 4 independent chains.
-// clamp_t: use max(t, 1e-8) (LearnedTimeDiffusion's in-place clamp_(min=1e-8) of the
-// parameter, upstream layers.py) and, in the forward, write it back (block 0; every block
-// computes the same value, so the concurrent reads see either value and use the clamped one).
-// gt (backward): this crop's dL/dt partial, written over the first row of its own partial
-// slab region (already consumed by this block) for the expand pass to sum in crop order.
-__global__ __launch_bounds__(1024) void spec_combine_kernel(float* __restrict__ part, int S,
-                                                            const float* __restrict__ evals,
-                                                            float* __restrict__ t, int clamp_t, int write_t,
-                                                            float* __restrict__ raw,
-                                                            float* __restrict__ scaled,
-                                                            const float* __restrict__ saved, int want_gt) {
-  __shared__ double gsum[16][kKC];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int c = tid & 63, k0 = (tid >> 6) * 4;
-  const float* pb = part + (int64_t)b * S * kKC * kKC + k0 * kKC + c;
-  const float tc = clamp_t ? fmaxf(t[c], 1e-8f) : t[c];
-  // the S slab partials (64 rows each) are summed in fp64: at N ~ 5000 CAD vertices a serial
-  // fp32 sum over ~80 slabs dominated the error of the diffusion-time gradient, a
-  // cancellation-prone contraction of two such sums
-  double v[4] = {0.0, 0.0, 0.0, 0.0};
-  int s = 0;
-  for (; s + 4 <= S; s += 4) {  // 4 slabs' loads issued together, added in slab order
-    float ld[4][4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) ld[u][i] = pb[(int64_t)(s + u) * kKC * kKC + i * kKC];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] += (double)ld[u][i];
-  }
-  for (; s < S; ++s) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] += (double)pb[(int64_t)s * kKC * kKC + i * kKC];
-  }
-  double g = 0.0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int k = k0 + i;
-    const float lam = evals[b * kKC + k];
-    const float E = expf(-lam * tc);
-    const int64_t o = (int64_t)b * kKC * kKC + k * kKC + c;
-    const float vf = (float)v[i];
-    if (raw) raw[o] = vf;
-    scaled[o] = E * vf;
-    if (want_gt) g = fma(-(double)lam * (double)E, (double)saved[o] * v[i], g);
-  }
-  if (write_t && b == 0 && tid < kKC) t[c] = tc;
-  if (want_gt) {
-    gsum[tid >> 6][c] = g;
-    __syncthreads();  // also orders this block's partial reads before the overwrite below
-    if (tid < kKC) {
-      double a = 0.0;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) a += gsum[q][c];
-      part[(int64_t)b * S * kKC * kKC + c] = (float)a;
-    }
-  }
-}
-
-// pass 3: y[r, :] = Phi[r, :] · coef (· mass[r] if given). grid (ceil(N/64), B), block 256:
-// 16 x 16 threads, 4 rows x 4 cols each.
-// gtb (backward): block (0, 0) also sums the per-crop dL/dt partials in crop order into gt.
-__global__ __launch_bounds__(256) void spec_expand_kernel(const float* __restrict__ evecs,
-                                                          const float* __restrict__ coef,
-                                                          const float* __restrict__ mass, int N,
-                                                          float* __restrict__ y, int ldy, int accumulate,
-                                                          const float* __restrict__ gtb, int64_t gt_stride,
-                                                          float* __restrict__ gt) {
-  __shared__ float4 scoef[kKC][kKC / 4];
-  __shared__ float sphi[64][kKC + 1];
-  const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int ty = tid >> 4, tx = tid & 15;
-  if (gt && tile == 0 && b == 0 && tid < kKC) {
-    float a = 0.f;
-    for (int q = 0; q < (int)gridDim.y; ++q) a += gtb[(int64_t)q * gt_stride + tid];
-    gt[tid] = a;
-  }
-  const float* __restrict__ cb = coef + (int64_t)b * kKC * kKC;
-  {
-    float4 cvv[kKC * kKC / 4 / 256];
-#pragma unroll
-    for (int j = 0; j < kKC * kKC / 4 / 256; ++j) cvv[j] = reinterpret_cast<const float4*>(cb)[tid + 256 * j];
-#pragma unroll
-    for (int j = 0; j < kKC * kKC / 4 / 256; ++j) scoef[(tid + 256 * j) / 16][(tid + 256 * j) % 16] = cvv[j];
-  }
-  const int r0 = tile * 64;
-  const float* __restrict__ phi = evecs + (int64_t)b * N * kKC;
-  {
-    float4 pvv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {  // unconditional at clamped rows, then selected
-      const int e = tid + 256 * j, rr = e / 16, q = e % 16;
-      const int r = r0 + rr < N ? r0 + rr : r0;
-      pvv[j] = reinterpret_cast<const float4*>(phi + (int64_t)r * kKC)[q];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int e = tid + 256 * j, rr = e / 16, q = e % 16;
-      const float4 v = r0 + rr < N ? pvv[j] : make_float4(0.f, 0.f, 0.f, 0.f);
-      sphi[rr][4 * q + 0] = v.x;
-      sphi[rr][4 * q + 1] = v.y;
-      sphi[rr][4 * q + 2] = v.z;
-      sphi[rr][4 * q + 3] = v.w;
-    }
-  }
-  // the epilogue's operands (mass, the accumulated output) in flight during the products
-  float wr[4];
-  float4 old[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = r0 + ty * 4 + i < N ? r0 + ty * 4 + i : r0;
-    wr[i] = mass ? mass[(int64_t)b * N + r] : 1.f;
-    old[i] = accumulate ? reinterpret_cast<const float4*>(y + ((int64_t)b * N + r) * ldy)[tx]
-                        : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  __syncthreads();
-  float acc[4][4] = {};
-#pragma unroll 8
-  for (int k = 0; k < kKC; ++k) {
-    const float4 cv = scoef[k][tx];
-    const float cc[4] = {cv.x, cv.y, cv.z, cv.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float p = sphi[ty * 4 + i][k];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(p, cc[j], acc[i][j]);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = r0 + ty * 4 + i;
-    if (r >= N) continue;
-    const float w = wr[i];
-    float4* yp = reinterpret_cast<float4*>(y + ((int64_t)b * N + r) * ldy) + tx;
-    float4 v = make_float4(acc[i][0] * w, acc[i][1] * w, acc[i][2] * w, acc[i][3] * w);
-    if (accumulate) {
-      const float4 o = old[i];
-      v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
-    }
-    *yp = v;
-  }
-}
-
-// ---- Round 4: passes 1 and 3 on the f32 MFMA (v_mfma_f32_16x16x4_f32). The scalar-FMA forms
-// above ran at 0.8-1.2 TB/s (0.10-0.15 of HBM) on these 8-17 MB passes; the products are 2 N K C
-// flops per crop, small next to the bytes, so the MFMA forms are bound by the row streams.
+// Passes 1 and 3 run on the f32 MFMA (v_mfma_f32_16x16x4_f32). The products are 2 N K C flops
+// per crop, small next to the bytes of these 8-17 MB passes, so they are bound by the row streams
+// (scalar-FMA forms ran at 0.10-0.15 of HBM).
 // Lane map as in attention.hip: A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15],
 // D[4 (l >> 4) + rr][l & 15]. Every lane loads whole float4s of a row, and the matrix indices are
 // permuted to match (documented per kernel), so no operand goes through LDS shuffles.
@@ -310,11 +109,18 @@ __global__ __launch_bounds__(256) void spec_reduce_mfma_kernel(const float* __re
   }
 }
 
-// pass 2 for the MFMA passes: spec_combine_kernel's sums over 4 x as many blocks (grid (B, 4),
-// block 1024: thread (k = 16 y + (tid >> 6), c = tid & 63) sums its one coefficient over the S
-// slabs in slab order, fp64, 8 slabs' loads in flight). gt (backward): block y's partial over its
-// 16 rows k goes to row 16 y of its crop's slab 0 (read by this block only, consumed before the
-// barrier); spec_expand_mfma_kernel adds the 4 per crop, then the crops, in order.
+// pass 2: coef = sum_s part; save raw (optional), scaled = E ⊙ coef; optional gt partial
+// gt[b, c] = -sum_k lambda_k E[k,c] saved[k,c] coef[k,c]. Grid (B, 4), block 1024: thread
+// (k = 16 y + (tid >> 6), c = tid & 63) sums its one coefficient over the S slabs in slab order,
+// 8 slabs' loads in flight. The sum is fp64: at N ~ 5000 CAD vertices a serial fp32 sum over the
+// slabs dominated the error of the diffusion-time gradient, a cancellation-prone contraction of
+// two such sums.
+// clamp_t: use max(t, 1e-8) (LearnedTimeDiffusion's in-place clamp_(min=1e-8) of the
+// parameter, upstream layers.py) and, in the forward, write it back (block (0, 0); every block
+// computes the same value, so the concurrent reads see either value and use the clamped one).
+// gt (backward): block y's partial over its 16 rows k goes to row 16 y of its crop's slab 0
+// (read by this block only, consumed before the barrier); spec_expand_mfma_kernel adds the 4 per
+// crop, then the crops, in order.
 __global__ __launch_bounds__(1024) void spec_combine4_kernel(float* __restrict__ part, int S,
                                                              const float* __restrict__ evals,
                                                              float* __restrict__ t, int clamp_t, int write_t,
@@ -498,15 +304,6 @@ __global__ __launch_bounds__(256) void spec_expand_mfma_kernel(const float* __re
   }
 }
 
-#ifdef PK_DEVBUILD
-static bool spec_scalar() {  // PK_SPEC_SCALAR=1: round 1's scalar-FMA passes 1 and 3 (A/B)
-  static const bool v = getenv("PK_SPEC_SCALAR") != nullptr && atoi(getenv("PK_SPEC_SCALAR")) != 0;
-  return v;
-}
-#else
-constexpr bool spec_scalar() { return false; }
-#endif
-
 }  // namespace
 
 // mode 0 (forward): in = x, out = y, raw = spec (saved for backward), reduce weights = mass.
@@ -522,37 +319,23 @@ extern "C" int pk_spectral_diffusion(const float* in, int ld_in, const float* ma
   PK_REQUIRE(in && evecs && evals && t && work && scaled && out);
   PK_REQUIRE(mode == 0 || (saved && gt));
   hipStream_t s = pk::as_stream(stream);
-  // slabs per crop: 64 rows each for the scalar passes, kCPB x 64 for the MFMA reduce
-  const int S = spec_scalar() ? (N + kRows - 1) / kRows : (N + kCPB * kRows - 1) / (kCPB * kRows);
-  if (spec_scalar())
-    hipLaunchKernelGGL(spec_reduce_kernel, dim3(S, B), dim3(256), 0, s, in, ld_in, mode == 0 ? mass : nullptr,
-                       evecs, N, S, work);
-  else
-    hipLaunchKernelGGL(spec_reduce_mfma_kernel, dim3(S, B), dim3(256), 0, s, in, ld_in,
-                       mode == 0 ? mass : nullptr, evecs, N, S, work);
+  const int S = (N + kCPB * kRows - 1) / (kCPB * kRows);  // slabs per crop
+  hipLaunchKernelGGL(spec_reduce_mfma_kernel, dim3(S, B), dim3(256), 0, s, in, ld_in, mode == 0 ? mass : nullptr,
+                     evecs, N, S, work);
   PK_CHECK_LAUNCH();
-  if (!spec_scalar() && mode == 0) {  // forward: the combine inside the expand (no third launch)
+  if (mode == 0) {  // forward: the combine inside the expand (no third launch)
     SpecFuse fz{work, S, clamp_t, (int)(clamp_t != 0), 0, evals, t, raw};
     hipLaunchKernelGGL(spec_expand_mfma_kernel<true>, dim3((N + 63) / 64, B), dim3(256), 0, s, evecs, scaled,
                        nullptr, N, out, ld_out, accumulate, work, (int64_t)S * kKC * kKC, nullptr, fz);
     PK_CHECK_LAUNCH();
     return PK_OK;
   }
-  if (spec_scalar())
-    hipLaunchKernelGGL(spec_combine_kernel, dim3(B), dim3(1024), 0, s, work, S, evals, t, clamp_t,
-                       (int)(clamp_t && mode == 0), raw, scaled, mode == 1 ? saved : nullptr, (int)(mode == 1));
-  else
-    hipLaunchKernelGGL(spec_combine4_kernel, dim3(B, 4), dim3(1024), 0, s, work, S, evals, t, clamp_t,
-                       (int)(clamp_t && mode == 0), raw, scaled, mode == 1 ? saved : nullptr, (int)(mode == 1));
+  // backward (mode 1 from here on)
+  hipLaunchKernelGGL(spec_combine4_kernel, dim3(B, 4), dim3(1024), 0, s, work, S, evals, t, clamp_t, 0, raw, scaled,
+                     saved, 1);
   PK_CHECK_LAUNCH();
-  if (spec_scalar())
-    hipLaunchKernelGGL(spec_expand_kernel, dim3((N + 63) / 64, B), dim3(256), 0, s, evecs, scaled,
-                       mode == 1 ? mass : nullptr, N, out, ld_out, accumulate, work, (int64_t)S * kKC * kKC,
-                       mode == 1 ? gt : nullptr);
-  else
-    hipLaunchKernelGGL(spec_expand_mfma_kernel<false>, dim3((N + 63) / 64, B), dim3(256), 0, s, evecs, scaled,
-                       mode == 1 ? mass : nullptr, N, out, ld_out, accumulate, work, (int64_t)S * kKC * kKC,
-                       mode == 1 ? gt : nullptr, SpecFuse{});
+  hipLaunchKernelGGL(spec_expand_mfma_kernel<false>, dim3((N + 63) / 64, B), dim3(256), 0, s, evecs, scaled, mass, N,
+                     out, ld_out, accumulate, work, (int64_t)S * kKC * kKC, gt, SpecFuse{});
   PK_CHECK_LAUNCH();
   return PK_OK;
 }

@@ -500,9 +500,11 @@ int pk_feat_dist_topk(const float* evecs_x, int ldx, const float* C, const float
  *   cand int64 [B,ldc,2] (cad idx, pc idx), ncand int32 [B]; cad f32 [B,ldcad,3],
  *   pc f32 [B,ldpc,3]; thr4 f32 [B,4] = diam * (0.3, 0.15, 0.055, 0.065)
  *   list_a/list_b int64 [B,ldc], n_a/n_b int32 [B], score f32 [B,ldc] scratch;
- *   partial f32 scratch of pk_rigidity_filter_work_size(B, nmax, ldc) bytes, or NULL: with it each
- *   unordered candidate pair is evaluated once (64 x 64 tile pairs, per-tile partial sums added in
- *   tile order); without it every candidate sums over all others itself.
+ *   partial f32 scratch of pk_rigidity_filter_work_size(B, nmax, ldc) bytes (any contents), or
+ *   NULL: with it the current list's coordinates are kept as packed records in the scratch and
+ *   each unordered candidate pair is evaluated once, tile pair by tile pair (the first round
+ *   shares one crop distance per pair of nn_query's 5-candidate groups; per-tile partial sums are
+ *   added in tile order); without it every candidate sums over all others itself, gathering through cand.
  * Result: survivors' candidate rows in list_b[b, :n_b[b]] (input order). */
 int64_t pk_rigidity_filter_work_size(int B, int nmax, int ldc);
 int pk_rigidity_filter(const int64_t* cand, int ldc, const int32_t* ncand, const float* cad, int ldcad,

@@ -55,6 +55,12 @@ def test_product_library_has_no_development_hooks():
     dev = nm(_lib.DEV_LIB_PATH)
     for hook in ("pkdev_seq_sum", "pkdev_rigidity_variant", "pkdev_probe_linear", "pkdev_fps_cfg"):
         assert hook in dev, hook
+    # and nothing else: a hook kept for a retired A/B comparison keeps its kernels in the library
+    defined = subprocess.run(["nm", "-D", "--defined-only", _lib.DEV_LIB_PATH], capture_output=True, text=True,
+                             check=True).stdout
+    hooks = {ln.split()[-1] for ln in defined.splitlines() if ln.split() and ln.split()[-1].startswith("pkdev_")}
+    assert hooks == {"pkdev_seq_sum", "pkdev_rigidity_variant", "pkdev_fps_cfg", "pkdev_probe_linear",
+                     "pkdev_probe_mfma", "pkdev_probe_mfma_order", "pkdev_probe_mfma_valu"}, sorted(hooks)
 
 
 def test_build_id_matches_tree():

@@ -214,6 +214,40 @@ def test_rigidity_filter_ragged_batch(device):
         _rigidity_parity(sc[0], sc[1], sc[2][:s], rows[i], int(n[i]), sc[3])
 
 
+def test_rigidity_filter_without_scratch(device):
+    """pk_rigidity_filter with partial = NULL (every candidate sums over the whole list itself,
+    gathering through cand): one ragged batch built as test_rigidity_filter_ragged_batch's, each
+    crop's survivors vs the oracle, and the packed path's result on the same inputs held to the
+    same check (so a crop the helper relaxes for threshold ties is relaxed for both)."""
+    from dpfm_amd import _lib, ops
+    sizes = [0, 1, 255, 257, 642]
+    scenes = [_rigid_scene(max((s + 4) // 5, 1), 7 + i) for i, s in enumerate(sizes)]
+    B, L = len(sizes), max(sizes)
+    cand = np.zeros((B, L, 2), dtype=np.int64)
+    for i, (s, sc) in enumerate(zip(sizes, scenes)):
+        cand[i, :s] = sc[2][:s]
+    dcand = torch.from_numpy(cand).to(device)
+    ncand = torch.tensor(sizes, dtype=torch.int32, device=device)
+    dcad = torch.from_numpy(np.stack([np.pad(sc[0], ((0, 600 - sc[0].shape[0]), (0, 0))) for sc in scenes])).to(device)
+    dpc = torch.from_numpy(np.stack([np.pad(sc[1], ((0, 600 - sc[1].shape[0]), (0, 0))) for sc in scenes])).to(device)
+    thr = ops.rigidity_thresholds([sc[3] for sc in scenes], device)
+    la, lb = (torch.zeros((B, L), dtype=torch.int64, device=device) for _ in range(2))
+    na, nb = (torch.empty((B,), dtype=torch.int32, device=device) for _ in range(2))
+    score = torch.empty((B, L), dtype=torch.float32, device=device)
+    _lib.call("pk_rigidity_filter", _lib.ptr(dcand), L, _lib.ptr(ncand), _lib.ptr(dcad), dcad.shape[1], _lib.ptr(dpc),
+              dpc.shape[1], _lib.ptr(thr), B, L, _lib.ptr(la), _lib.ptr(lb), _lib.ptr(na), _lib.ptr(nb),
+              _lib.ptr(score), None, _lib.stream(device))
+    rows_p, n_p = ops.rigidity_filter(dcand, ncand, dcad, dpc, thr)
+    rows, n = lb.cpu().numpy(), nb.cpu().numpy()
+    rows_p, n_p = rows_p.cpu().numpy(), n_p.cpu().numpy()
+    assert n[0] == 0 and n_p[0] == 0
+    for i, (s, sc) in enumerate(zip(sizes, scenes)):
+        if s == 0:
+            continue
+        _rigidity_parity(sc[0], sc[1], sc[2][:s], rows[i], int(n[i]), sc[3])
+        _rigidity_parity(sc[0], sc[1], sc[2][:s], rows_p[i], int(n_p[i]), sc[3])
+
+
 def _rigid_dev(dl, variant, cand, ncand, cad, pc, thr):
     """pk_rigidity_filter of the dev library under pkdev_rigidity_variant(variant): (survivor
     rows, counts, the last round's scores)."""

@@ -17,8 +17,8 @@ def _packed(arrs, dtype, device):
 
 @pytest.mark.parametrize("sizes,grid", [
     ([1, 7, 100, 1024, 2049, 4500, 9000, 13000, 14000, 20000, 26000], False),  # > 13312: per-lane buckets, plain
-    ([1, 7, 100, 1024, 2049, 4500, 9000, 13000], False),         # pruned buckets, random order
-    ([500, 3000, 8000, 13312], True),                             # pruned, spatially coherent runs
+    ([1, 7, 100, 1024, 2049, 4500, 9000, 13000], False),         # flat kernel's lane boxes, random order
+    ([500, 3000, 8000, 13312], True),                             # flat, spatially coherent runs
     ([300, 2649, 5100, 9289], True),                              # 10 points per lane (<= 10,240)
     ([9, 600, 10240], False),
 ])

@@ -10,7 +10,7 @@ import torch  # noqa: E402
 
 blocks = int(sys.argv[1]) if len(sys.argv) > 1 else 7
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
-if os.environ.get("PK_DEV") == "1":  # PK_BQ_VAR store-flavour A/B (tools/bq_ab.sh)
+if os.environ.get("PK_DEV") == "1":  # libposekern_dev.so (the PK_DIAG_* / PK_SIDE_PRIO diagnostics of csrc/common.hpp)
     from dpfm_amd import _lib
     _lib.use_dev_lib()
 dev = torch.device("cuda:0")

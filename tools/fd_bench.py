@@ -14,7 +14,7 @@ import torch  # noqa: E402
 
 from dpfm_amd import _lib, ops  # noqa: E402
 
-if os.environ.get("PK_DEV") == "1":  # libposekern_dev.so (its PK_FD_* switches)
+if os.environ.get("PK_DEV") == "1":  # libposekern_dev.so (the PK_DIAG_* / PK_SIDE_PRIO diagnostics of csrc/common.hpp)
     _lib.use_dev_lib()
 from dpfm_amd.dataset.synthetic import lbo_operators  # noqa: E402
 

@@ -45,7 +45,6 @@ for step in "$@"; do
                grep "^{\"metric\"" "$out/steptrace_to_bench.log" | tail -1 > "$out/steptrace_to.json"
                python tools/step_window_summary.py $(find "$out/steptrace_to" -name "*kernel_trace.csv" | head -1) "$out/steptrace_to.json" > "$out/step_window_summary_train_only.txt" 2>&1
                find "$out/steptrace_to" -type f -delete ;;
-    fdstamps) PK_FD_VAR=13 run fdstamps 200 python tools/fd_stamps.py ;;
     mvprobe) run mvprobe 200 python tools/mfma_valu_probe.py ;;
     moprobe) run moprobe 200 python tools/mfma_order_probe.py ;;
     pmcstep) TAG=$tag/pmcstep run pmcstep 700 bash tools/pmc_step.sh ;;

@@ -46,14 +46,13 @@ for B, npt in [(32, 1024)]:
     ms = timeit(lambda: ops.fps_packed(x, off, nin, st, npv, npt), iters=5, warm=1)
     print(f"fps (dispatch) B={B} n_in<={nin} npoint={npt}: {ms:.3f} ms  ({ms*1e3/npt:.3f} us/iter)")
     out = torch.zeros((B, npt), dtype=torch.int64, device=dev)
-    for pruned in ((4, 6) if os.environ.get("KB_FAST") else (4, 3, 1, 0)):
-        for nt in ((1024,) if os.environ.get("KB_FAST") else (256, 512, 1024)):
-            f = lambda: L.pkdev_fps_cfg(_lib.ptr(x), _lib.ptr(off), B, nin, _lib.ptr(st), _lib.ptr(npv), _lib.ptr(out),
-                                        npt, nt, pruned, _lib.stream(dev))
-            if f() != 0:
-                continue
-            ms = timeit(f, iters=20, warm=5)
-            print(f"   pruned={pruned} nt={nt}: {ms:.3f} ms ({ms*1e3/npt:.3f} us/iter) same={torch.equal(out, ref)}")
+    for mode in (4, 3):  # the flat and the per-lane kernel, whatever the dispatch would pick
+        f = lambda: L.pkdev_fps_cfg(_lib.ptr(x), _lib.ptr(off), B, nin, _lib.ptr(st), _lib.ptr(npv), _lib.ptr(out),
+                                    npt, 1024, mode, _lib.stream(dev))
+        if f() != 0:
+            continue
+        ms = timeit(f, iters=20, warm=5)
+        print(f"   mode={mode}: {ms:.3f} ms ({ms*1e3/npt:.3f} us/iter) same={torch.equal(out, ref)}")
 
 if len(sys.argv) > 1 and sys.argv[1] == "fps":
     sys.exit(0)
@@ -71,22 +70,12 @@ for B, N in [(32, 1024), (256, 2048)]:
     ms = timeit(f)
     byts = B * (24 * N + 24 * N + N * N)
     print(f"ball_query_mask (f32 screen) B={B} N={N}: {ms:.3f} ms, {byts/ms/1e6:.1f} GB/s algorithmic")
-    m1 = mask.clone(); r1 = rc.clone()
-    from dpfm_amd import _lib
-    f64 = lambda: _lib.lib().pkdev_ball_query_mask64(ptr(cad), ptr(off), ptr(pc), ptr(off), ptr(thr), B, N, N, ptr(mask), ld, ptr(rc), s)
-    ms = timeit(f64)
-    print(f"ball_query_mask (all fp64) B={B} N={N}: {ms:.3f} ms, {byts/ms/1e6:.1f} GB/s algorithmic; same={torch.equal(m1, mask) and torch.equal(r1, rc)}")
-    fv1 = lambda: _lib.lib().pkdev_ball_query_mask_v1(ptr(cad), ptr(off), ptr(pc), ptr(off), ptr(thr), B, N, N, ptr(mask), ld, ptr(rc), s)
-    ms = timeit(fv1)
-    print(f"ball_query_mask (v1 f32 screen) B={B} N={N}: {ms:.3f} ms, {byts/ms/1e6:.1f} GB/s algorithmic; same={torch.equal(m1, mask) and torch.equal(r1, rc)}")
     # dense case: a large share of the pairs within r, many near the boundary
     thr_d = torch.full((B,), ops.ball_threshold(8.0), dtype=torch.float64, device=dev)
     fd = lambda: call("pk_ball_query_mask", ptr(cad), ptr(off), ptr(pc), ptr(off), ptr(thr_d), B, N, N, ptr(mask), ld, ptr(rc), s)
     ms = timeit(fd)
-    md = mask.clone(); rd = rc.clone()
-    _lib.lib().pkdev_ball_query_mask64(ptr(cad), ptr(off), ptr(pc), ptr(off), ptr(thr_d), B, N, N, ptr(mask), ld, ptr(rc), s)
-    print(f"ball_query_mask dense (r=8, {float(rd.double().mean())/N:.3f} in) B={B} N={N}: {ms:.3f} ms, "
-          f"{byts/ms/1e6:.1f} GB/s; same as fp64={torch.equal(md, mask) and torch.equal(rd, rc)}")
+    print(f"ball_query_mask dense (r=8, {float(rc.double().mean())/N:.3f} in) B={B} N={N}: {ms:.3f} ms, "
+          f"{byts/ms/1e6:.1f} GB/s")
     f2 = lambda: ops.ball_query(cad, off, pc, off, [0.6] * B, N, N, 64 * N, thr2=thr)
     ms = timeit(f2)
     print(f"ball_query full (mask+scan+pairs) B={B} N={N}: {ms:.3f} ms")
@@ -94,8 +83,7 @@ for B, N in [(32, 1024), (256, 2048)]:
     ms = timeit(f3)
     print(f"ball_query fused (count+scan+pairs, no mask) B={B} N={N}: {ms:.3f} ms")
 
-# per-point layer weight gradients: direct-load MFMA kernel vs the LDS-staged v1
-L.pkdev_linear_wgrad_v1.argtypes = [c for i, c in enumerate(_lib.SIGNATURES["pk_linear_wgrad"]) if i != 10]  # no accumulate arg
+# per-point layer weight gradients
 for (R_or_B, I, O, N, cf) in [(65536, 128, 64, 0, False), (65536, 64, 64, 0, False), (65536, 64, 32, 0, False),
                               (32, 64, 64, 1024, True), (32, 32, 32, 1024, True)]:
     if cf:
@@ -106,19 +94,9 @@ for (R_or_B, I, O, N, cf) in [(65536, 128, 64, 0, False), (65536, 64, 64, 0, Fal
         x = torch.randn(R_or_B, I, device=dev)
         dy = torch.randn(R_or_B, O, device=dev)
         R = R_or_B
-    dw, db = ops.linear_wgrad(x, dy, channels_first=cf)
     ms2 = timeit(lambda: ops.linear_wgrad(x, dy, channels_first=cf))
-    S = (R + 127) // 128
-    work = torch.empty((S * (O * I + O),), device=dev)
-    dw1 = torch.empty((O, I), device=dev)
-    db1 = torch.empty((O,), device=dev)
-    f1 = lambda: L.pkdev_linear_wgrad_v1(_lib.ptr(x), _lib.ptr(dy), int(cf), R, I, O, N, _lib.ptr(work), _lib.ptr(dw1),
-                                         _lib.ptr(db1), _lib.stream(dev))
-    ms1 = timeit(f1)
-    rel = float((dw - dw1).abs().max() / dw1.abs().max())
     fl = 2.0 * R * I * O
-    print(f"linear_wgrad R={R} I={I} O={O} {'cf' if cf else 'cl'}: v2 {ms2*1e3:.1f} us ({fl/ms2/1e9:.1f} TF/s) "
-          f"v1 {ms1*1e3:.1f} us; max rel diff {rel:.2e}")
+    print(f"linear_wgrad R={R} I={I} O={O} {'cf' if cf else 'cl'}: {ms2*1e3:.1f} us ({fl/ms2/1e9:.1f} TF/s)")
 
 # per-point layer forward / input gradient: pk_linear_fwd vs the library GEMM (+ bias)
 for (R_or_B, I, O, N, cf) in [(65536, 128, 64, 0, False), (65536, 64, 128, 0, False), (65536, 3, 64, 0, False),

@@ -6,7 +6,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "6d-pose-estimation-for-unseen-categori
 import torch
 from dpfm_amd import _lib, ops
 
-if os.environ.get("PK_DEV") == "1":  # libposekern_dev.so (its PK_* switches, e.g. PK_ROWS_GLDS=0)
+if os.environ.get("PK_DEV") == "1":  # libposekern_dev.so (the PK_DIAG_* / PK_SIDE_PRIO diagnostics of csrc/common.hpp)
     _lib.use_dev_lib()
 
 dev = torch.device("cuda:0")

@@ -12,7 +12,7 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 from dpfm_amd import _lib, ops  # noqa: E402
 
-if os.environ.get("PK_DEV") == "1":  # libposekern_dev.so (its PK_* switches, e.g. PK_WG_GLDS=0)
+if os.environ.get("PK_DEV") == "1":  # libposekern_dev.so (the PK_DIAG_* / PK_SIDE_PRIO diagnostics of csrc/common.hpp)
     _lib.use_dev_lib()
 
 sys.argv = ["bench.py"]

@@ -4,7 +4,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "6d-pose-estimation-for-unseen-categories_amd")]
 import torch
 from dpfm_amd import _lib, ops
-if os.environ.get("PK_DEV") == "1":  # libposekern_dev.so (PK_SOR_OLD=1: the round-6 kNN kernel)
+if os.environ.get("PK_DEV") == "1":  # libposekern_dev.so (the PK_DIAG_* / PK_SIDE_PRIO diagnostics of csrc/common.hpp)
     _lib.use_dev_lib()
 from dpfm_amd.pipeline import make_frame_batch
 

@@ -2,7 +2,7 @@
 forward (mode 0, mass-weighted reduce) and backward (mode 1, mass on the expand, accumulate),
 graph-free back-to-back launches with HIP events; algorithmic bytes = Phi read twice + the
 input rows + the output rows (+ the accumulated rows). With PK_DEV=1 the dev library is loaded
-(PK_SPEC_SCALAR=1: round 1's scalar-FMA passes).
+(the diagnostics of csrc/common.hpp).
 
   python tools/spec_bench.py [B] [N]
 """
@@ -57,5 +57,4 @@ def timed(fn, it=50):
 for name, fn, nb in (("forward", fwd, 4 * B * N * 64 * 4), ("backward", bwd, 4 * B * N * 64 * 5)):
     us = timed(fn)
     print(f"spectral {name} B={B} N={N} (3 launches): {us:6.1f} us  {nb / 1e6:5.1f} MB -> "
-          f"{nb / us / 1e6:5.2f} TB/s ({nb / us / 1e6 / 8.0:.3f} of HBM)  "
-          f"PK_SPEC_SCALAR={os.environ.get('PK_SPEC_SCALAR', '-')}")
+          f"{nb / us / 1e6:5.2f} TB/s ({nb / us / 1e6 / 8.0:.3f} of HBM)")

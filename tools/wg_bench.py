@@ -1,7 +1,7 @@
 """Grouped weight gradients (pk_linear_wgrad_grouped) on the training step's call list at configs[1]
 (tools/lin_census.py: 28 calls, 6.34 GFLOP), timed back to back with HIP events; prints us per
 group, the algorithmic bytes (every x and dy read once) and FLOP rates against the MI355X peaks.
-With PK_DEV=1 the dev library is loaded (PK_WG_GLDS=0: round 3's per-tile-wave kernel).
+With PK_DEV=1 the dev library is loaded (the diagnostics of csrc/common.hpp).
 
   python tools/wg_bench.py [iters] [--each]   (--each: every shape group alone as well)
 """
@@ -66,8 +66,7 @@ def line(name, us, nb, fl):
 if os.environ.get("WG_ONLY"):  # one shape group alone (its index in spec), e.g. under rocprofv3
     name, calls, nbytes, flops = groups[int(os.environ["WG_ONLY"])]
     print(f"group {name}")
-print(f"device: {torch.cuda.get_device_properties(0).multi_processor_count} CUs; "
-      f"PK_WG_BUDGET={os.environ.get('PK_WG_BUDGET', '-')} PK_WG_GLDS={os.environ.get('PK_WG_GLDS', '-')}")
+print(f"device: {torch.cuda.get_device_properties(0).multi_processor_count} CUs")
 print("wgrad grouped " + line(f"({len(calls)} calls)", timed(calls), nbytes, flops))
 if "--each" in sys.argv:
     for name, cl, nb, fl in groups:
