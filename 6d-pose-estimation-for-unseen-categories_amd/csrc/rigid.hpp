@@ -71,8 +71,9 @@ __host__ __device__ __forceinline__ double det3(double a0, double a1, double a2,
 // root of det(N - l I) = l^4 + c2 l^2 + c1 l + c0 (c2 = -2 |S|_F^2, c1 = -8 det S, c0 = det N)
 // by Newton from the upper bound |S|_F sqrt(3) >= the nuclear norm of S >= l_max (monotone
 // from above), then the eigenvector as the largest column of adj(N - l I). Returns false when
-// that column is tiny relative to the scale (a near-multiple top eigenvalue: 4 draws with a
-// repeated or collinear correspondence), where the caller falls back to Jacobi.
+// that column is small relative to the scale (a close or multiple top eigenvalue: a near-collinear
+// draw, two distinct points, a few coplanar or repeated-correspondence draws), where the caller
+// falls back to Jacobi.
 __host__ __device__ inline bool top_eigvec4_qcp(const double N[4][4], const double S[3][3], double q[4]) {
   double f2 = 0.0;
 #pragma unroll
@@ -139,9 +140,12 @@ __host__ __device__ inline bool top_eigvec4_qcp(const double N[4][4], const doub
 #pragma unroll
     for (int i = 0; i < 4; ++i) q[i] = take ? v[i] : q[i];
   }
-  // |adj| ~ product of the three eigen-gaps (<= (2 l)^3): tiny means a near-multiple root
+  // |adj| ~ product of the three eigen-gaps (<= (2 l)^3). Newton finds a root with relative gap g
+  // only to ~eps / g (a double root to ~sqrt(eps)), and the adjugate column taken there is off by
+  // ~eps / g^2: accepted for g above ~1e-3 (|adj|^2 > 1e-6 scale^2), where that stays within the
+  // eps / g the rotation is determined to; 1e-8 already loses 20x on near-collinear draws.
   const double scale = 8.0 * l * l * l;
-  return best > 1e-16 * scale * scale;
+  return best > 1e-6 * scale * scale;
 }
 
 // R (row-major) and t with d ≈ R s + t from the centred cross-covariance S (any positive

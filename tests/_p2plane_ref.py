@@ -33,16 +33,10 @@ def knn_brute(P, k):
     return out
 
 
-def normals_ref(P, k=30, viewpoint=(0.0, 0.0, 0.0), order="seq", knn=None):
-    """-> (normals [n,3], gap [n] = (l1 - l0) / l2 of the covariance's ascending eigenvalues;
-    inf where the normal is the fixed (0,0,1))."""
-    n = P.shape[0]
-    nrm = np.zeros((n, 3))
-    nrm[:, 2] = 1.0
-    gap = np.full(n, np.inf)
-    kk = min(k, n)
-    if kk < 3:
-        return nrm, gap
+def cov_ref(P, k=30, order="seq", knn=None):
+    """[n,3,3]: the covariance of each point's min(k, n) neighbours about the point itself,
+    C = S2 / m - mean mean^T, summed in neighbour order (order="rev": reversed)."""
+    kk = min(k, P.shape[0])
     nb = (knn_brute(P, k) if knn is None else knn)[:, :kk]
     E = P[nb] - P[:, None, :]                      # [n, kk, 3]
     if order == "rev":
@@ -50,8 +44,19 @@ def normals_ref(P, k=30, viewpoint=(0.0, 0.0, 0.0), order="seq", knn=None):
     s = np.cumsum(E, axis=1)[:, -1]                # sequential sums
     S2 = np.cumsum(E[:, :, :, None] * E[:, :, None, :], axis=1)[:, -1]
     m = s / kk
-    C = S2 / kk - m[:, :, None] * m[:, None, :]
-    w, V = np.linalg.eigh(C)
+    return S2 / kk - m[:, :, None] * m[:, None, :]
+
+
+def normals_ref(P, k=30, viewpoint=(0.0, 0.0, 0.0), order="seq", knn=None):
+    """-> (normals [n,3], gap [n] = (l1 - l0) / l2 of the covariance's ascending eigenvalues;
+    inf where the normal is the fixed (0,0,1))."""
+    n = P.shape[0]
+    nrm = np.zeros((n, 3))
+    nrm[:, 2] = 1.0
+    gap = np.full(n, np.inf)
+    if min(k, n) < 3:
+        return nrm, gap
+    w, V = np.linalg.eigh(cov_ref(P, k, order, knn))
     nrm = V[:, :, 0].copy()
     nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
     flip = np.einsum("nc,nc->n", nrm, np.asarray(viewpoint, np.float64)[None] - P) < 0

@@ -129,6 +129,30 @@ def test_ransac_matches_c_oracle(device, coracle):
         assert np.abs(res.transformation[:3, :3] - R).max() < 1e-2  # and it found the pose
 
 
+@pytest.mark.parametrize("trial", range(3))
+def test_ransac_planar_object_matches_c_oracle(device, coracle, trial):
+    """test_ransac_matches_c_oracle on a flat CAD (tests/_rigid_ref.py::planar_ransac_case): every
+    one of the 512 hypotheses is a coplanar draw, so every fit is a rank-2 S. The winner, its
+    fitness and rmse are the C oracle's (test_rigid_ref_cpu.py checks on the oracle alone that the
+    best two hypotheses differ in fitness or in rmse by > 1e-6; the rmse itself is compared to
+    1e-9: the two fits differ in their last bits), T within the 1e-4 pose tolerance."""
+    from _util import cp
+    import _rigid_ref as RR
+    from dpfm_amd.pose.ransac import ransac_registration
+    data_seed, seed = RR.PLANAR_TRIALS[trial]
+    cad, pc, corres, R, _ = RR.planar_ransac_case(data_seed)
+    T_c = np.zeros(16)
+    st_c = np.zeros(3)
+    coracle.oc_ransac(cp(cad), cp(pc), cp(corres), corres.shape[0], None, seed, RR.PLANAR_H, RR.PLANAR_MAX_DIST,
+                      cp(T_c), cp(st_c))
+    res = ransac_registration(cad, pc, corres, distance_threshold=RR.PLANAR_MAX_DIST, max_iteration=RR.PLANAR_H,
+                              seed=seed, device=device)
+    assert res.best_hypothesis == int(st_c[2])
+    assert res.fitness == st_c[0]
+    assert abs(res.inlier_rmse - st_c[1]) <= 1e-9
+    np.testing.assert_allclose(res.transformation, T_c.reshape(4, 4), atol=1e-4)  # north-star pose tolerance
+
+
 def test_ransac_explicit_hypotheses_and_degenerate(device, coracle):
     from dpfm_amd.pose.ransac import ransac_registration
     rng = np.random.default_rng(9)

@@ -8,6 +8,9 @@ suite pins against the numpy restatement of Open3D's loop (test_oracle_cpu.py::t
   * the reference's own setting on its real data (tests/golden/real_crops.npz): source = CAD
     (~5000 vertices), target = the CAD under T_gt (test_RANSAC.py:426-436), threshold 0.2,
     init = T_gt perturbed; and the build's crop-target variant (CAD against the observed crop);
+  * exact planes (an integer-millimetre fronto-parallel plane, and the same plane tilted): every
+    update's cross-covariance has rank 2; source and target on one line (rank 1): the rotation is
+    not unique, so fitness and rmse are compared and T only has to be rigid;
   * edge cases: no pair within the radius, an empty target, max_iteration 0, and the blocking
     C entry point pk_icp against the host-polled loop.
 """
@@ -106,6 +109,54 @@ def test_icp_real_crops_matches_oracle(coracle, device, target):
         tgts.append(np.ascontiguousarray(tgt))
         T0s.append(_perturb(rng, Tg, 2.0, 0.1, tgt.mean(0)))
     _check(coracle, srcs, tgts, T0s, 0.2, 2000, device)
+
+
+def integer_plane(rng, n=400):
+    """A fronto-parallel surface in integer-millimetre depth: x, y = round(U(-300, 300)), z = 900."""
+    return np.ascontiguousarray(np.concatenate([np.round(rng.uniform(-300, 300, size=(n, 2))), np.full((n, 1), 900.0)], 1))
+
+
+def test_icp_exact_planes_match_oracle(coracle, device):
+    """Every update's cross-covariance has rank 2 exactly (rigid_from_cov on coplanar pairs): the
+    integer plane, and the same plane tilted; source = 250 of the target's points, started 2
+    degrees / 3 mm off, radius 20."""
+    from dpfm_amd.dataset.synthetic import random_rotation
+    rng = np.random.default_rng(12)
+    flat = integer_plane(rng)
+    tilted = np.ascontiguousarray(flat @ random_rotation(rng).T)
+    srcs, tgts, T0s = [], [], []
+    for tgt in (flat, tilted):
+        src = np.ascontiguousarray(tgt[rng.permutation(400)[:250]])
+        srcs.append(src)
+        tgts.append(tgt)
+        T0s.append(_perturb(rng, np.eye(4), 2.0, 3.0, src.mean(0)))
+    T, st = _check(coracle, srcs, tgts, T0s, 20.0, 100, device)
+    assert (st[:, 3] == 1).all() and (st[:, 0] == 1.0).all()
+
+
+def test_icp_collinear_points_match_oracle_stats(coracle, device):
+    """Source and target on one line: every update's cross-covariance has rank 1, the rotation
+    about the line is free (T is not compared), and neither the fitness nor the inlier rmse depends
+    on it. T stays a rigid transform (R R^T = I and det R = 1 to 64 eps; the oracle stops after 9
+    updates with 3 eps)."""
+    from dpfm_amd import ops
+    rng = np.random.default_rng(13)
+    u = rng.normal(size=3)
+    u /= np.linalg.norm(u)
+    tgt = np.ascontiguousarray(np.array([10.0, -20.0, 900.0]) + rng.uniform(-300, 300, size=(400, 1)) * u)
+    src = np.ascontiguousarray(tgt[rng.permutation(400)[:250]])
+    T0 = _perturb(rng, np.eye(4), 2.0, 3.0, src.mean(0))
+    s, so = _pack([src], device)
+    t, to = _pack([tgt], device)
+    T, st = ops.icp(s, so, t, to, torch.from_numpy(T0[None]).to(device), 20.0, 30)
+    T, st = T.cpu().numpy()[0], st.cpu().numpy()[0]
+    To, sto = _oracle(coracle, src, tgt, T0, 20.0, 30)
+    print(f"device {st.tolist()} oracle {sto.tolist()}")
+    assert abs(st[0] - sto[0]) <= 1e-9 and abs(st[1] - sto[1]) <= 1e-9 and st[0] > 0.9
+    eps = np.finfo(np.float64).eps
+    Rm = T[:3, :3]
+    assert np.isfinite(T).all() and (T[3] == [0, 0, 0, 1]).all()
+    assert np.abs(Rm @ Rm.T - np.eye(3)).max() <= 64 * eps and abs(np.linalg.det(Rm) - 1) <= 64 * eps
 
 
 def test_icp_edge_cases(coracle, device):

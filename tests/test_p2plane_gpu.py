@@ -11,6 +11,9 @@ recorded in DESIGN.md §4:
     target, 1.22e-14 rad on the blob; the bar is 100x the larger one, 1.22e-12 rad. Left out
     below the gap: none of the 1500 ellipsoid points (smallest gap 0.16), none of the 1500 blob
     points (smallest gap 0.018);
+  * normals where the covariance's smallest eigenvalue is exactly 0 or repeated (derived bars, see
+    test_normals_on_degenerate_neighbourhoods): exact on an integer-millimetre plane, 64 eps
+    lmax / lmid on its tilt, the Rayleigh quotient on a line, one point and an octahedron;
   * point-to-plane ICP with the restatement's normals passed in: update count, converged flag
     and fitness equal, rmse and T within 1e-9 (the restatement against itself, every sum
     reversed: at most 1.1e-13 in T and 1.8e-15 in rmse over the cases below, same update counts);
@@ -185,6 +188,80 @@ def test_normals_match_restatement(device):
     assert (sgn < 0).any() and (sgn > 0).any()
     np.testing.assert_array_equal(far, nrm[:o[2]] * sgn[:, None])
     np.testing.assert_array_equal(estimate_normals(clouds[1], device=device), nrm[o[1]:o[2]])
+
+
+EPS = float(np.finfo(np.float64).eps)
+
+
+def degenerate_crops():
+    """Neighbourhoods whose covariance has an exactly zero or a repeated smallest eigenvalue:
+    (a) a fronto-parallel plane in integer-millimetre depth, z = 900 (what every real frame holds);
+    (b) the same plane tilted by a random rotation;
+    (c) points on a line; (d) 64 copies of one point;
+    (e) an octahedron: 6 copies of a centre and 4 of each vertex centre +- e_i, the 30 nearest
+        neighbours of a centre copy (C = (8/30) I exactly at k = 30), and 34 points far outside.
+    -> crops, the tilted plane's unit normal."""
+    from dpfm_amd.dataset.synthetic import random_rotation
+    rng = np.random.default_rng(31)   # a seed whose plane has no collinear 3-neighbourhood
+    plane = np.concatenate([np.round(rng.uniform(-300, 300, size=(400, 2))), np.full((400, 1), 900.0)], 1)
+    Rm = random_rotation(rng)
+    u = rng.normal(size=3)
+    u /= np.linalg.norm(u)
+    line = np.array([10.0, -20.0, 900.0]) + rng.uniform(-300, 300, size=(100, 1)) * u
+    same = np.tile(np.array([[12.5, -7.25, 903.0]]), (64, 1))
+    c = np.array([3.0, 4.0, 900.0])
+    far = rng.normal(size=(34, 3))
+    octa = np.concatenate([np.tile(c, (6, 1))] + [np.tile(c + sg * e, (4, 1)) for e in np.eye(3) for sg in (1.0, -1.0)] +
+                          [c + 50.0 * far / np.linalg.norm(far, axis=1, keepdims=True)])
+    crops = [plane, plane @ Rm.T, line, same, octa[rng.permutation(64)]]
+    return [np.ascontiguousarray(x) for x in crops], Rm[:, 2].copy()
+
+
+@pytest.mark.parametrize("k", [30, 3])
+def test_normals_on_degenerate_neighbourhoods(device, k):
+    """min_eigvec3 where the smallest eigenvalue is exactly 0 or not simple (one call for all crops).
+    Planes: the normal itself — exactly (0, 0, -1) on the integer plane (every ez is exactly 0, so
+    the covariance's z row is exactly 0 and no Jacobi rotation touches it), within 64 eps lmax /
+    lmid of the true normal on the tilted one. Line, one point, octahedron: the normal is not
+    unique; it is a unit vector towards the viewpoint whose Rayleigh quotient is the smallest
+    eigenvalue."""
+    from dpfm_amd import ops
+    crops, tilt = degenerate_crops()
+    p, off = _pack(crops, device)
+    nrm, knn = ops.estimate_normals(p, off, k=k, return_knn=True)
+    nrm, knn, o = nrm.cpu(), knn.cpu().numpy(), off.cpu().numpy()
+    # (a)
+    flat = nrm[o[0]:o[1]]
+    gap = R.normals_ref(crops[0], k)[1]
+    assert gap.min() > 1e-6   # no neighbourhood of the seed's plane is collinear: the in-plane eigenvalues are > 0
+    assert torch.equal(flat, torch.tensor([0.0, 0.0, -1.0], dtype=torch.float64).expand(400, 3))
+    nrm = nrm.numpy()
+    # (b)
+    gap = R.normals_ref(crops[1], k)[1]
+    true = np.tile(tilt if tilt @ -crops[1][0] > 0 else -tilt, (400, 1))
+    ang = _angles(nrm[o[1]:o[2]], true)
+    bar = 64 * EPS / gap + 1e-15
+    i = int(np.argmax(ang / bar))
+    print(f"k = {k}: tilted plane: angle {ang[i]:.3e} / {bar[i]:.3e} at point {i} (lmid / lmax {gap[i]:.3e})")
+    assert gap.min() > 1e-6 and (ang <= bar).all()
+    # (c) - (e)
+    for b, what in ((2, "line"), (3, "one point"), (4, "octahedron")):
+        P, n = crops[b], nrm[o[b]:o[b + 1]]
+        C = R.cov_ref(P, k)
+        w = np.linalg.eigvalsh(C)
+        assert np.isfinite(n).all(), what
+        assert np.abs(np.linalg.norm(n, axis=1) - 1).max() <= 8 * EPS, what
+        ray = np.einsum("ni,nij,nj->n", n, C, n)
+        i = int(np.argmax(ray - w[:, 0] - 64 * EPS * w[:, 2]))
+        print(f"k = {k}: {what}: Rayleigh {ray[i]:.3e}, lmin {w[i, 0]:.3e}, lmax {w[i, 2]:.3e} at point {i}")
+        assert (ray <= w[:, 0] + 64 * EPS * w[:, 2]).all(), what
+        assert (np.einsum("nc,nc->n", n, -P) >= -8 * EPS * np.linalg.norm(P, axis=1)).all(), what
+    # equal distances: the (d^2, index) order
+    np.testing.assert_array_equal(knn[o[3]:o[4]], R.knn_brute(crops[3], k))
+    if k == 30:   # the octahedron's centre copies see the isotropic neighbourhood
+        centre = np.nonzero((crops[4] == np.array([3.0, 4.0, 900.0])).all(1))[0]
+        C = R.cov_ref(crops[4], 30)[centre]
+        assert centre.size == 6 and (C == np.eye(3) * C[0, 0, 0]).all() and C[0, 0, 0] > 0
 
 
 def test_plane_icp_matches_restatement(device, icp_cases):
