@@ -904,6 +904,7 @@ __global__ __launch_bounds__(256) void fd_top1_merge_kernel(const unsigned long 
 constexpr int kT5Slots = 16;
 constexpr int kT5Tasks = 1536;  // rows recomputed per block (E3b)
 constexpr int kT5X = 8;         // recomputed rows below a column's fifth key kept for its merge (E3c)
+constexpr int kT5MaxRows = 1 << 24;  // V1max of the mode-0 top-5: E3b's task entries hold the row tile in 20 bits
 
 // the exact distance of row `row` (tile t, in-tile i) and block column jj, as the MFMA chain forms it
 __device__ __forceinline__ float t5_exact(const f32x4* __restrict__ Ab, int t, int i, const f32x4 (*sB)[2][64],
@@ -1197,8 +1198,15 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
   const int n = colok ? sCnt[col] : 0;
   bool slow = n > kT5Slots;
   // each candidate's rank among the column's n by (value, row) (keys are unique: distinct rows);
-  // ranks 0..4 are the five, written in place (the four threads are lanes of one wave: LDS
-  // program order, no barrier)
+  // ranks 0..4 are the five, written in place. The four threads are lanes of one wave; a
+  // wavefront-scope fence and a wave barrier order thread 0's init stores before the others' rank
+  // stores, and those before the read-back (no wait is added on gfx950: the LDS keeps a wave's
+  // program order; the fences keep the compiler to it)
+  auto wave_sync = [] {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
   if (qd == 0) {
 #pragma unroll
     for (int q = 0; q < 5; ++q) {
@@ -1206,6 +1214,7 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
       sBsl[col][q] = -1;
     }
   }
+  wave_sync();
   if (!slow) {
     unsigned long long kl[kT5Slots];  // the column's list in registers (entries past n: never smaller)
 #pragma unroll
@@ -1225,6 +1234,7 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
     }
   }
   slow = t5_any4(slow);
+  wave_sync();
 #pragma unroll
   for (int q = 0; q < 5; ++q) {
     best[q] = sBest[col][q];
@@ -1253,6 +1263,9 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
         tbase = atomicAdd(&sNtask, tcnt);
         if (tbase + tcnt > kT5Tasks) {
           sXflag[col] = 1;  // (task list full: the slow path takes the column)
+          // the reservation that straddles the end still owns its slots below kT5Tasks: E3b walks
+          // them, so they hold the skip entry (one past the end reserves none)
+          for (int k = tbase; k < kT5Tasks; ++k) sTask[k] = -1;
           tcnt = 0;
         } else {
           int k = tbase;
@@ -1265,9 +1278,16 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
   __syncthreads();
   {  // E3b: every listed row's exact distance, one per thread; the few below the column's fifth
      // key go to its short list (any other can never enter the five)
+    // sTask invariant: the reservations partition [0, sNtask); one that ends at or below kT5Tasks
+    // wrote a task (t << 11 | col << 4 | i, t < 2^20: never negative) into each of its slots, the
+    // one that straddles kT5Tasks wrote -1 into its slots below it, and those past it own none. So
+    // every slot below min(sNtask, kT5Tasks) was written by this block before the barrier above:
+    // a task of a row of this crop, or -1 (skipped; its column is flagged for the slow path).
     const int ntask = min(sNtask, kT5Tasks);
     for (int k = tid; k < ntask; k += 64 * kTop1Waves) {
-      const int d = sTask[k], t = d >> 11, cc = (d >> 4) & (NC - 1), i = d & 15;
+      const int d = sTask[k];
+      if (d < 0) continue;
+      const int t = d >> 11, cc = (d >> 4) & (NC - 1), i = d & 15;
       const float v = t5_exact(Ab, t, i, sB, cc);
       const unsigned long long key = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)(t * 16 + i);
       if (__float_as_int(v) <= kClampBits) {
@@ -1425,6 +1445,7 @@ inline FdPlan fd_plan(int B, int V1max, int V2max, int topk, int mode) {
 
 extern "C" int64_t pk_feat_dist_work_size(int B, int V1max, int V2max, int topk, int mode) {
   if (B < 0 || V1max < 0 || V2max < 0 || !(topk == 1 || topk == 5) || mode < 0 || mode > 2) return -1;
+  if (mode == 0 && topk == 5 && V1max > kT5MaxRows) return -1;
   const FdPlan p = fd_plan(B, V1max, V2max, topk, mode);
   const int64_t two_pass = p.a_bytes + p.b_bytes + p.na_bytes + p.nb_bytes + p.pv_bytes + p.pi_bytes;
   if (mode != 0) return two_pass;
@@ -1441,6 +1462,7 @@ extern "C" int pk_feat_dist_topk(const float* evecs_x, int ldx, const float* C, 
                                  void* stream) {
   PK_REQUIRE(B >= 0 && V1max >= 0 && V2max >= 0 && ldx >= kF && ldy >= kF && (topk == 1 || topk == 5));
   PK_REQUIRE(mode >= 0 && mode <= 2);
+  PK_REQUIRE(!(mode == 0 && topk == 5) || V1max <= kT5MaxRows);
   if (B == 0 || V2max == 0) return PK_OK;
   PK_REQUIRE(evecs_x && C && evecs_y && n1 && n2 && out_idx);
   const int64_t need = pk_feat_dist_work_size(B, V1max, V2max, topk, mode);

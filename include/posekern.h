@@ -488,6 +488,8 @@ int pk_linear_ex2(const pk_linear_args* a0, const pk_linear_args* a1, void* stre
  *     or writes row-part keys that a second launch merges — no arrival words, no zeroing contract;
  *     round 6: the mode-0 top-5 pass likewise — exact five per column, recomputing only the rows
  *     of kept streams that may hold more members; row parts merged by a second launch).
+ *   mode 0 with topk = 5 requires V1max <= 2^24: above it pk_feat_dist_work_size returns -1 and
+ *     pk_feat_dist_topk PK_ERR_ARG.
  *   out_idx int64 [B,V2max,topk] ascending distance (ties: lower index); out_dist f32
  *   [B,V2max,topk] Euclidean distances (may be NULL). Fused selection epilogue. */
 int64_t pk_feat_dist_work_size(int B, int V1max, int V2max, int topk, int mode);

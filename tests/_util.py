@@ -226,19 +226,36 @@ def train_step_parity(M, op, crops, device, model_seed, step_seed):
         assert ee[2] <= 3 * max(ee[0], ee[1]) + floor, (name, ee, floor, t.norm().item())
 
 
+def fma_f32(a, b, c):
+    """fmaf(a, b, c) on float32 arrays, correctly rounded (normal results). The product of two
+    f32 is exact in float64; s = f64(p + c) and TwoSum's e with p + c = s + e exactly. Casting s to
+    f32 rounds a second time, which goes wrong only where s lies exactly on an f32 rounding midpoint
+    (its low 29 mantissa bits are 1 then 28 zeros) while the true sum does not (e != 0): there s
+    moves one f64 ulp towards e, off the midpoint and to the true sum's side, before the cast."""
+    a, b, c = np.broadcast_arrays(np.asarray(a, np.float32), np.asarray(b, np.float32), np.asarray(c, np.float32))
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c = c.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = p + c
+        bb = s - p
+        e = (p - (s - bb)) + (c - bb)
+    mid = ((s.view(np.int64) & 0x1FFFFFFF) == 0x10000000) & np.isfinite(s) & (e != 0)
+    if mid.any():
+        s = np.where(mid, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+    with np.errstate(over="ignore"):
+        return s.astype(np.float32)
+
+
 def fd_emulate(ex, C, ey, n1: int, n2: int):
     """The fp32 feature-distance pass's distances [n1, n2], emulated on the host: the prep's -2 emb
     = -2 x C^T and |emb|^2, the columns' [y, 1, |y|^2], and the contraction as ONE fmaf chain over
     the 32 slots in the MFMA's order (v_mfma_f32_16x16x4f32 accumulates exactly so:
     tools/mfma_order_probe.py). Slot (s, g) holds feature 16 (s >> 2) + 4 g + (s & 3); slot (6, 3)
-    is |emb|^2 x 1, slot (7, 3) is 1 x |y|^2. fmaf is emulated in float64 (exact product, the sum
-    rounded to f64 and then to f32: a double rounding can differ from fmaf in 1 ulp, rarely)."""
+    is |emb|^2 x 1, slot (7, 3) is 1 x |y|^2. fmaf is exact (fma_f32 above)."""
     ex = np.asarray(ex, np.float32)[:n1, :30]
     ey = np.asarray(ey, np.float32)[:n2, :30]
     C = np.asarray(C, np.float32)
-
-    def fma(a, b, c):
-        return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+    fma = fma_f32
 
     order = [(s, g) for s in range(8) for g in range(4)]
     kid = [16 * (s >> 2) + 4 * g + (s & 3) for s, g in order]
