@@ -101,6 +101,8 @@ SIGNATURES = {
     "pk_feat_dist_work_size": [_I, _I, _I, _I, _I],
     "pk_attention_bwd_work_size": [_I, _I, _I, _I, _I],
     "pk_feat_dist_topk": [_P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I64, _P, _P, _P],
+    "pk_zoomout_work_size": [_I, _I, _I, _I, _I],
+    "pk_zoomout": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I64, _P, _P, _P],
     "pk_rigidity_filter_work_size": [_I, _I, _I],
     "pk_rigidity_filter": [_P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "pk_inlier_ratio": [_P, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P, _P, _P],
@@ -159,7 +161,7 @@ RESTYPES = {"pk_cgt_lstsq_work_size": _I64, "pk_linear_wgrad_grouped_work": _I64
             "pk_feat_dist_work_size": _I64, "pk_fmap_head_work_len": _I64, "pk_icp_work_size": _I64,
             "pk_rigidity_filter_work_size": _I64, "pk_attention_bwd_work_size": _I64,
             "pk_normals_work_size": _I64, "pk_icp_plane_work_size": _I64,
-            "pk_teaser_scale_work_size": _I64}  # everything else returns an int status
+            "pk_teaser_scale_work_size": _I64, "pk_zoomout_work_size": _I64}  # everything else returns an int status
 
 _lib: Optional[ctypes.CDLL] = None
 _dev_lib: Optional[ctypes.CDLL] = None

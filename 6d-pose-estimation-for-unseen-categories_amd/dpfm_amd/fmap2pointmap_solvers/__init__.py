@@ -5,6 +5,7 @@
 returns the solver it is given (default: the spatial-filtering solver)."""
 from .naive import naive_fmap2pointmap, nn_query
 from .spacial_filtering import spacial_filtering_fmap2pointmap, spacial_filtering
+from .zoomout import zoomout_refine, zoomout_fmap2pointmap, zoomout_spacial_filtering_fmap2pointmap
 
 
 def choose_fmap2pointmap_solver(solver=None):

@@ -1007,6 +1007,63 @@ def feat_dist_topk(evecs_x: torch.Tensor, C: torch.Tensor, evecs_y: torch.Tensor
     return idx, dist
 
 
+ZOOMOUT_K0 = 30    # the size of the map ZoomOut starts from (n_fmap)
+ZOOMOUT_KMAX = 64  # eigenvectors held per shape
+ZOOMOUT_SLAB = 64  # crop rows per partial sum of the projection (csrc/zoomout.hip kSlab)
+
+
+def zoomout_schedule(k_final: int, step: int) -> list[int]:
+    """The map sizes ZoomOut visits: 30, 30 + step, ..., k_final (the last step may be short)."""
+    ks = [ZOOMOUT_K0]
+    while ks[-1] < k_final:
+        ks.append(min(ks[-1] + step, k_final))
+    return ks
+
+
+def zoomout(evecs_x: torch.Tensor, evecs_y: torch.Tensor, mass_y: torch.Tensor, C0: torch.Tensor,
+            n1: torch.Tensor, n2: torch.Tensor, k_final: int = 64, step: int = 1,
+            work: Optional[torch.Tensor] = None):
+    """ZoomOut refinement of a 30 x 30 functional map (pk_zoomout; Melzi et al. 2019): alternates the
+    point map p[j] = argmin_i |evecs_x[i, :k] C^T - evecs_y[j, :k]| (naive.py's convention, ties to the
+    lowest i) with C = evecs_y[:, :k]^T diag(mass_y) evecs_x[p, :k] at the next k = min(k + step,
+    k_final). evecs_x [B,V1,K>=k_final], evecs_y [B,V2,K>=k_final], mass_y [B,V2], C0 [B,30,30],
+    n1/n2 int32 [B]. Returns (C f32 [B,k_final,k_final], p2p int64 [B,V2]; rows j >= n2 are 0).
+    work: optional caller scratch (uint8, any contents, nothing kept across calls)."""
+    for t in (evecs_x, evecs_y, mass_y, C0, n1, n2):
+        if not t.is_cuda:
+            raise _lib.PoseKernError("zoomout takes HIP device tensors only (no CPU fallback)")
+    k_final, step = int(k_final), int(step)
+    if evecs_x.dim() != 3 or evecs_y.dim() != 3 or evecs_x.shape[0] != evecs_y.shape[0]:
+        raise _lib.PoseKernError("zoomout: evecs_x [B,V1,K] and evecs_y [B,V2,K] expected")
+    B, V1, ldx = evecs_x.shape
+    _, V2, ldy = evecs_y.shape
+    if not ZOOMOUT_K0 <= k_final <= ZOOMOUT_KMAX or k_final > min(ldx, ldy):
+        raise _lib.PoseKernError(f"zoomout: k_final must lie in 30..64 and within the evecs' width "
+                                 f"({min(ldx, ldy)}), got {k_final}")
+    if step < 1:
+        raise _lib.PoseKernError(f"zoomout: step must be >= 1, got {step}")
+    if tuple(C0.shape) != (B, ZOOMOUT_K0, ZOOMOUT_K0) or tuple(mass_y.shape) != (B, V2):
+        raise _lib.PoseKernError("zoomout: C0 [B,30,30] and mass_y [B,V2] expected")
+    if n1.numel() != B or n2.numel() != B or n1.dtype != torch.int32 or n2.dtype != torch.int32:
+        raise _lib.PoseKernError("zoomout: n1 / n2 must be int32 [B]")
+    dev = evecs_x.device
+    step = min(step, ZOOMOUT_KMAX)
+    nbytes = int(_lib.lib().pk_zoomout_work_size(B, V1, V2, k_final, step))
+    if nbytes < 0:
+        raise _lib.PoseKernError("zoomout: invalid shape")
+    if work is None:
+        work = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+    elif work.numel() < nbytes:
+        raise _lib.PoseKernError(f"zoomout: work holds {work.numel()} bytes, {nbytes} needed")
+    C = torch.empty((B, k_final, k_final), dtype=torch.float32, device=dev)
+    p2p = torch.empty((B, V2), dtype=torch.int64, device=dev)
+    flops = sum(2 * B * V1 * V2 * 4 * ((k + 3) // 4) for k in zoomout_schedule(k_final, step))
+    call("pk_zoomout", ptr(evecs_x.float().contiguous()), ldx, ptr(evecs_y.float().contiguous()), ldy,
+         ptr(mass_y.float().contiguous()), ptr(C0.float().contiguous()), ptr(n1), ptr(n2), B, V1, V2, k_final, step,
+         ptr(work), nbytes, ptr(C), ptr(p2p), _lib.stream(dev), work=("mfma", flops))
+    return C, p2p
+
+
 def nce_select(counts: torch.Tensor, cap: int, num: int, seed: int, ctr: torch.Tensor):
     """pk_nce_select: rows int64 [B, k], valid bool [B, k], k = min(num, cap); advances ctr."""
     B = counts.shape[0]

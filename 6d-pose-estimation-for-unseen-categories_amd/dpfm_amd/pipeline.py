@@ -231,6 +231,21 @@ def naive_p2p_batched(C: torch.Tensor, evecs_x: torch.Tensor, evecs_y: torch.Ten
     return torch.stack([idx[..., 0], ar], 1)
 
 
+def zoomout_p2p_batched(C: torch.Tensor, evecs_x: torch.Tensor, evecs_y: torch.Tensor, mass_y: torch.Tensor,
+                        n1: Optional[torch.Tensor] = None, n2: Optional[torch.Tensor] = None,
+                        k_final: int = 64, step: int = 1):
+    """ZoomOut refinement (ops.zoomout) of every crop's 30 x 30 map: (C f32 [B, k_final, k_final],
+    p2p int64 [B, 2, V2]) with p2p shaped like naive_p2p_batched's (row 0 CAD idx, row 1 arange;
+    entries j >= n2[b] of row 0 are 0)."""
+    B, V1, _ = evecs_x.shape
+    V2 = evecs_y.shape[1]
+    dev = C.device
+    Czo, p = ops.zoomout(evecs_x, evecs_y, mass_y, C, _counts(n1, B, V1, dev), _counts(n2, B, V2, dev),
+                         k_final=k_final, step=step)
+    ar = torch.arange(V2, device=dev, dtype=torch.int64)[None].expand(B, V2)
+    return Czo, torch.stack([p, ar], 1)
+
+
 class TrainStep:
     """One training iteration (scripts/train.py:88-124) for a batch of crops.
 
@@ -686,7 +701,7 @@ class InferStep:
 
     def __init__(self, model: DPFMNet, hypotheses: int = 1024, seed: int = 0, max_dist: float = 0.05,
                  icp_evaluations: int = 0, icp_threshold: float = 0.2, masked: bool = False,
-                 icp_estimation: str = "point_to_point", bop_metrics: bool = False):
+                 icp_estimation: str = "point_to_point", bop_metrics: bool = False, zoomout=None):
         """icp_evaluations > 0 refines each RANSAC pose by point-to-point ICP of the CAD against the
         observed crop (test_RANSAC.py:436-446 runs ICP after RANSAC, against the GT-posed CAD; the
         crop is the target available without ground truth), with that many evaluations enqueued
@@ -696,8 +711,16 @@ class InferStep:
         TransformationEstimationPointToPlane.
         bop_metrics=True adds the BOP pose errors of the same T / T_gt / fb.K with the frame batch's
         symmetry sets (ops.bop_errors): `bop` f64 [B, 3] = (MSSD, MSPD, ADI), `bop_best` int32 [B, 2],
-        and `bop_icp` for the refined pose when ICP is on. Off: the output dict is unchanged."""
+        and `bop_icp` for the refined pose when ICP is on. Off: the output dict is unchanged.
+        zoomout=(k_final, step) refines C_pred by ZoomOut (ops.zoomout with the crop's op.pc_mass; no
+        counterpart in the reference) and hands the rigidity filter the refined point map, one candidate
+        per crop point (cand [B, V2, 2], ncand = n2), in place of the top-5; the output dict gains
+        `C_zo` f32 [B, k_final, k_final]. None: every launch and every output as without it."""
         self.bop_metrics = bool(bop_metrics)
+        self.zoomout = None if zoomout is None else (int(zoomout[0]), int(zoomout[1]))
+        if self.zoomout is not None and not (ops.ZOOMOUT_K0 <= self.zoomout[0] <= ops.ZOOMOUT_KMAX
+                                             and self.zoomout[1] >= 1):
+            raise ValueError(f"zoomout must be None or (k_final in 30..64, step >= 1), got {zoomout!r}")
         if icp_estimation not in ops.ICP_ESTIMATIONS:
             raise ValueError(f"icp_estimation must be one of {ops.ICP_ESTIMATIONS}, got {icp_estimation!r}")
         self.model, self.H, self.seed, self.max_dist = model, hypotheses, seed, max_dist
@@ -709,7 +732,14 @@ class InferStep:
 
     @torch.no_grad()
     def __call__(self, fb: FrameBatch, op: Operators, crops: Crops):
-        return self.pose_stage(fb, op, crops, self.model_stage(fb, op, crops))
+        return self.staged(fb, op, crops, self.model_stage(fb, op, crops))
+
+    def staged(self, fb: FrameBatch, op: Operators, crops: Crops, m: dict) -> dict:
+        """pose_stage on model_stage's outputs, plus the outputs only the model stage holds."""
+        out = self.pose_stage(fb, op, crops, m)
+        if "C_zo" in m:
+            out["C_zo"] = m["C_zo"]
+        return out
 
     @torch.no_grad()
     def model_stage(self, fb: FrameBatch, op: Operators, crops: Crops) -> dict:
@@ -723,6 +753,11 @@ class InferStep:
         # eval.py:85-87: the solver sees only the non-padding rows of each crop
         n1 = _counts(op.cad_n, B, V1, dev)
         n2 = _counts(crops.n2, B, V2, dev)
+        if self.zoomout is not None:
+            C_zo, p = ops.zoomout(op.cad_evecs, op.pc_evecs, op.pc_mass, C_pred, n1, n2, k_final=self.zoomout[0],
+                                  step=self.zoomout[1])
+            cand = torch.stack([p, torch.arange(V2, device=dev)[None].expand(B, V2)], -1)
+            return dict(C=C_pred, cand=cand, ncand=n2, C_zo=C_zo)
         top, _ = ops.feat_dist_topk(op.cad_evecs, C_pred, op.pc_evecs, n1, n2, 5)      # spacial_filtering.py:32-38
         cand = torch.stack([top.reshape(B, -1),
                             torch.arange(V2, device=dev)[None, :, None].expand(B, V2, 5).reshape(B, -1)], -1)
@@ -856,7 +891,7 @@ class PipelinedInfer:
             if stages == 3:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    self.outs.append(infer.pose_stage(fb, op, self.crops[k], self.mids[k]))
+                    self.outs.append(infer.staged(fb, op, self.crops[k], self.mids[k]))
                 self.pose_graphs.append(g)
         self.formed = [torch.cuda.Event() for _ in range(nb)]
         self.modeled = [torch.cuda.Event() for _ in range(nb)]

@@ -497,6 +497,29 @@ int pk_feat_dist_topk(const float* evecs_x, int ldx, const float* C, const float
                       const int32_t* n1, const int32_t* n2, int B, int V1max, int V2max, int topk, int mode,
                       void* work, int64_t work_bytes, int64_t* out_idx, float* out_dist, void* stream);
 
+/* ZoomOut spectral refinement of the functional map (Melzi et al. 2019, "ZoomOut: Spectral
+ * Upsampling for Efficient Shape Correspondence"; pyFM's zoomout_refine), with the map -> point
+ * map conversion of fmap2pointmap_solvers/naive.py:6-34 (X the CAD, Y the crop). The reference
+ * repository has no ZoomOut: a build-defined addition. With k = 30 at the start:
+ *   1. E = evecs_x[:n1, :k] C^T;  p[j] = argmin_{i < n1} (|E_i|^2 - 2 E_i . evecs_y[j, :k])  (j < n2;
+ *      ties: the lowest i)
+ *   2. k == k_final: stop;  else k <- min(k + step, k_final)
+ *   3. C[a, b] = sum_{j < n2} mass_y[j] evecs_y[j, a] evecs_x[p[j], b]  (a, b < k);  go to 1.
+ *   evecs_x f32 [B,V1max,ldx], evecs_y f32 [B,V2max,ldy] (ldx, ldy >= k_final), mass_y f32
+ *   [B,V2max], C0 f32 [B,30,30], n1/n2 int32 [B] valid rows; 30 <= k_final <= 64, step >= 1.
+ *   C_out f32 [B,k_final,k_final] (k_final = 30: C0; n2 = 0: zeros); p2p int64 [B,V2max], rows
+ *   j >= n2 written as 0; no index is >= n1.
+ *   work: scratch of pk_zoomout_work_size(...) bytes (-1: invalid arguments), any contents:
+ *     nothing in it is read before this call writes it and nothing is kept across calls. No
+ *     atomics: a crop's result is bit-identical from call to call and does not depend on the
+ *     batch around it. The whole schedule (a host function of k_final and step only) is enqueued
+ *     on `stream` without a host read: capturable. */
+int64_t pk_zoomout_work_size(int B, int V1max, int V2max, int k_final, int step);
+int pk_zoomout(const float* evecs_x, int ldx, const float* evecs_y, int ldy, const float* mass_y,
+               const float* C0, const int32_t* n1, const int32_t* n2, int B, int V1max, int V2max,
+               int k_final, int step, void* work, int64_t work_bytes, float* C_out, int64_t* p2p,
+               void* stream);
+
 /* H11 rigidity filter (fmap2pointmap_solvers/spacial_filtering.py:42-75), three rounds
  * on device with the 0.055 -> 0.065 fallback.
  *   cand int64 [B,ldc,2] (cad idx, pc idx), ncand int32 [B]; cad f32 [B,ldcad,3],
