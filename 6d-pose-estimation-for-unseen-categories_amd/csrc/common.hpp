@@ -178,6 +178,9 @@ __device__ __forceinline__ float f32_unordered(uint32_t u) {
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Bytes rounded up to the 256-byte granule at which the entry points carve their scratch.
+__host__ __device__ inline int64_t al256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+
 }  // namespace pk
 
 namespace pk {

@@ -18,475 +18,22 @@
 // Modes 1 / 2 are opt-in (configs[4]'s "4096 x 4096 bf16"); tests report their argmin
 // agreement with mode 0.
 //
-// Pass 1 (prep): one thread per row computes the row's operand (x side: emb = x C^T, an fmaf
-// chain over k in order; y side: y) and its squared norm, and writes the operand straight
-// into MFMA operand-tile order (16-row tiles, lane l = 16 g + c holding row c's k values of
-// its group g), so pass 2 moves whole tiles with 16-byte loads and no transposes.
-// Pass 2 (main, fd_main_direct_kernel): a block = 4 waves over 4 column tiles and the block's
-// row tiles; each wave takes 2 column tiles (B operands in registers) and half the rows, and
-// streams its rows' fragments from L2 into registers one chunk ahead of the MFMAs (every A
-// fragment feeds two accumulation chains). Epilogue per 16 x 16 tile: running argmin / sorted
-// top-5 per column (ties: lowest row); the two row halves merge through LDS at the end. With
-// RS > 1 the blocks' row parts write partial lists that pass 3 merges (same tie rule), so one
-// 4096-point crop (configs[4]) still spreads over the chip.
-// Mode 0 on 16-byte-aligned operand rows takes the one-pass kernels further down instead
-// (fd_top1_prep_kernel, then fd_top1_kernel / fd_top5_kernel); the two passes above serve modes
-// 1 and 2 and unaligned mode-0 inputs.
+// This unit: the two entry points and the one-pass fp32 path, which mode 0 takes on 16-byte-aligned
+// operand rows: fd_top1_prep_kernel (the row operands, once per 16-row tile), then fd_top1_kernel
+// (argmin) or fd_top5_kernel (top-5), which finish every column of a block inside the block. The
+// two kernels share their layout, and its pieces are defined once between them: the block
+// numbering (fd_crop_block, featdist.hpp), the wave's row tiles (top1_wave_tiles), the operand
+// loads (top1_opload / top1_unpack), the column staging (top1_col_load, top1_stage_partials / top1_stage_operands) and the
+// software-pipelined tile loop (top1_tile_loop, a template over the selection); they differ in the
+// selection per distance and in what follows the loop. Modes 1 and 2 and unaligned mode-0 inputs
+// take the two-pass path of featdist_twopass.hip.
 #include <algorithm>
 
-#include "common.hpp"
-#include "mfma_tile.hpp"
+#include "featdist.hpp"
 
 namespace {
 
-constexpr int kF = 30;   // n_fmap
-constexpr int kK = 32;   // contraction length (K padded)
-constexpr int kCW = 1;   // column tiles per wave
-constexpr int kWaves = 4;
-constexpr int kCH = 8;   // row tiles per LDS stage
-using pk::f32x4;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-
-// bytes of one 16-row operand tile per mode (f32: 64 lanes x 8 floats; bf16: 64 x 8 bf16;
-// bf16x3: hi then lo)
-__host__ __device__ constexpr int tile_bytes(int mode) { return mode == 0 ? 2048 : mode == 1 ? 1024 : 2048; }
-
-__device__ __forceinline__ __bf16 to_bf16(float v) { return (__bf16)v; }
-
-// grid (ceil(max(T1, T2) / 8), B, 2), block 512: wave = one 16-row tile of one side (z = 0:
-// x side, 1: y side). Lane (g, c) = (lane >> 4, lane & 15).
-//   x side: emb = x C^T on the f32 MFMA ([16 x 32] x [32 x 32], two 16 x 16 output tiles,
-//           K = 30 zero-padded; an f32 MFMA accumulates as the fmaf chain over k in order),
-//           then through LDS into the operand layout;
-//   y side: y itself.
-// The squared norm of a row is its lane group's 8 values summed per lane, then across the 4
-// lanes of the row (fixed order). Rows >= n (and the tile padding) are written as zeros.
-constexpr int kPrepWaves = 8;  // one 16-row tile per wave, 8 waves per block
-
-template <int MODE>
-__global__ __launch_bounds__(64 * kPrepWaves) void fd_prep_kernel(const float* __restrict__ ex, int ldx,
-                                                      const float* __restrict__ C, const float* __restrict__ ey,
-                                                      int ldy, const int32_t* __restrict__ n1,
-                                                      const int32_t* __restrict__ n2, int V1max, int V2max, int T1,
-                                                      int T2, char* __restrict__ A, char* __restrict__ Bq,
-                                                      float* __restrict__ nA, float* __restrict__ nB) {
-  __shared__ float E[kPrepWaves][16][kK + 1];  // per wave: the tile's rows (emb or y), k padded to 32
-  const int b = blockIdx.y;
-  const bool xside = blockIdx.z == 0;
-  const int w = pk::wave_id(), lane = pk::lane_id(), g = lane >> 4, c16 = lane & 15;
-  const int T = xside ? T1 : T2;
-  const int tile = blockIdx.x * kPrepWaves + w;
-  if (tile >= T) return;
-  const int r = tile * 16 + c16;
-  // every operand load is issued before the first wait: the row at a clamped index (its
-  // validity against n applied by select afterwards), the C entries (both sides: C is tiny),
-  // and n itself — a load addressed through n, or behind the x-side branch, would add a round
-  // trip each
-  const float* rowp = xside ? ex + ((int64_t)b * V1max + min(r, V1max - 1)) * ldx
-                            : ey + ((int64_t)b * V2max + min(r, V2max - 1)) * ldy;
-  // this lane's 8 row values at k = 4 s + g (the f32 MFMA operand layout), 0 past k = 29
-  float xv[8];
-  float cvs[2][8];
-#pragma unroll
-  for (int s = 0; s < 8; ++s) xv[s] = rowp[min(4 * s + g, kF - 1)];
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int s = 0; s < 8; ++s)
-      cvs[n][s] = C[((int64_t)b * kF + min(16 * n + c16, kF - 1)) * kF + min(4 * s + g, kF - 1)];
-  const int nval = xside ? n1[b] : n2[b];
-  const bool valid = r < nval;
-  // the empty asm pins the loads above this point (else the compiler sinks them under the
-  // select / the x-side branch, behind a wait of their own)
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int s = 0; s < 8; ++s) asm volatile("" : "+v"(cvs[n][s]));
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    asm volatile("" : "+v"(xv[s]));
-    xv[s] = (valid && 4 * s + g < kF) ? xv[s] : 0.f;
-  }
-  float (*Ew)[kK + 1] = E[w];
-  if (xside) {
-    // D[row 4 g' + q][col c] of output tile n: emb[row][16 n + c] = sum_k x[row][k] C[16 n + c][k]
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      const int cc = 16 * n + c16;
-#pragma unroll
-      for (int s = 0; s < 8; ++s)
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[s], (cc < kF && 4 * s + g < kF) ? cvs[n][s] : 0.f, acc, 0, 0, 0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) Ew[4 * g + q][cc] = acc[q];
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < 8; ++s) Ew[c16][4 * s + g] = xv[s];
-  }
-  __builtin_amdgcn_s_waitcnt(0);
-  __builtin_amdgcn_wave_barrier();
-  // the lane's operand values (mode 0: k = 4 s + g; bf16 modes: k = 8 g + j) and the row norm
-  float v[8];
-  float part = 0.f;
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    const int k = MODE == 0 ? 4 * s + g : 8 * g + s;
-    v[s] = (valid && k < kF) ? Ew[c16][k] : 0.f;
-    part = fmaf(v[s], v[s], part);
-  }
-  const float p1 = __shfl_xor(part, 16), p2 = __shfl_xor(part, 32), p3 = __shfl_xor(part, 48);
-  const float mine[4] = {part, p1, p2, p3};  // lane group g, g^1, g^2, g^3
-  float nrm = 0.f;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) nrm += mine[q ^ g];  // groups 0, 1, 2, 3 in that order
-  // padding rows: y side zeros; x side a row whose distance to every column is +inf (mode 0:
-  // the |x|^2 slot; bf16 modes: the norm), so the main pass needs no row mask
-  if (!valid) nrm = xside ? __builtin_huge_valf() : 0.f;
-  char* base = (xside ? A + (int64_t)b * T1 * tile_bytes(MODE) : Bq + (int64_t)b * T2 * tile_bytes(MODE)) +
-               (int64_t)tile * tile_bytes(MODE);
-  if (MODE == 0) {
-    // augmented operand: x side [-2 emb, |emb|^2, 1], y side [y, 1, |y|^2]
-    float o[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) o[s] = xside ? -2.f * v[s] : v[s];
-    if (g >= 2 && valid) o[7] = (xside == (g == 2)) ? nrm : 1.f;  // k = 30 (g = 2), 31 (g = 3)
-    if (g == 2 && xside && !valid) o[7] = nrm;                      // +inf |x|^2 slot
-    float4* d = reinterpret_cast<float4*>(base + (size_t)lane * 32);
-    d[0] = make_float4(o[0], o[1], o[2], o[3]);
-    d[1] = make_float4(o[4], o[5], o[6], o[7]);
-  } else {
-    // bf16 cross-term operand: x side -2 emb, y side y (k < 30, zero pad); k = 8 g + j
-    bf16x8 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float f = xside ? -2.f * v[j] : v[j];
-      const __bf16 h = to_bf16(f);
-      hi[j] = h;
-      lo[j] = to_bf16(f - (float)h);
-    }
-    *reinterpret_cast<bf16x8*>(base + (size_t)lane * 16) = hi;
-    if (MODE == 2) *reinterpret_cast<bf16x8*>(base + 1024 + (size_t)lane * 16) = lo;
-    if (g == 0) (xside ? nA + (int64_t)b * T1 * 16 : nB + (int64_t)b * T2 * 16)[r] = nrm;
-  }
-}
-
-template <int TOPK>
-struct TopK {
-  float v[TOPK];
-  int i[TOPK];
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int k = 0; k < TOPK; ++k) {
-      v[k] = __builtin_huge_valf();
-      i[k] = 0x7fffffff;
-    }
-  }
-  // rows arrive in increasing index order: strict < keeps the lowest index on ties
-  __device__ __forceinline__ void push(float x, int idx) {
-    if (TOPK == 1) {
-      const bool lt = x < v[0];
-      v[0] = lt ? x : v[0];
-      i[0] = lt ? idx : i[0];
-      return;
-    }
-    if (!(x < v[TOPK - 1])) return;
-    float cv = x;
-    int ci = idx;
-#pragma unroll
-    for (int k = 0; k < TOPK; ++k) {
-      const bool sw = cv < v[k];
-      const float tv = sw ? v[k] : cv;
-      const int ti = sw ? i[k] : ci;
-      v[k] = sw ? cv : v[k];
-      i[k] = sw ? ci : i[k];
-      cv = tv;
-      ci = ti;
-    }
-  }
-  // merge an incoming sorted list (ties: lower index first)
-  __device__ __forceinline__ void merge(const float (&ov)[TOPK], const int (&oi)[TOPK]) {
-#pragma unroll
-    for (int k = 0; k < TOPK; ++k) {
-      float cv = ov[k];
-      int ci = oi[k];
-#pragma unroll
-      for (int m = 0; m < TOPK; ++m) {
-        const bool sw = cv < v[m] || (cv == v[m] && ci < i[m]);
-        const float tv = sw ? v[m] : cv;
-        const int ti = sw ? i[m] : ci;
-        v[m] = sw ? cv : v[m];
-        i[m] = sw ? ci : i[m];
-        cv = tv;
-        ci = ti;
-      }
-    }
-  }
-};
-
-// 4 distances of this lane (rows ibase .. ibase + 3 of its column) into the running top-k
-template <int TOPK>
-__device__ __forceinline__ void epilogue(const float (&d)[4], int ibase, TopK<TOPK>& best) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) best.push(fmaxf(d[r], 1e-30f), ibase + r);  // clamp_min(1e-30) (cdist mm path)
-}
-
-template <int TOPK>
-__device__ __forceinline__ void lanegroup_merge(TopK<TOPK>& best) {
-#pragma unroll
-  for (int off = 16; off <= 32; off <<= 1) {
-    float ov[TOPK];
-    int oi[TOPK];
-#pragma unroll
-    for (int k = 0; k < TOPK; ++k) {
-      ov[k] = __shfl_xor(best.v[k], off);
-      oi[k] = __shfl_xor(best.i[k], off);
-    }
-    best.merge(ov, oi);
-  }
-}
-
-// One 16 x 16 tile (rows of A tile `a`, this wave's column tile) -> 4 values per lane
-// (rows 4 g + r, column c16).
-template <int MODE>
-struct Frag;
-template <> struct Frag<0> { float a[8]; };
-template <> struct Frag<1> { bf16x8 hi; float n[4]; };
-template <> struct Frag<2> { bf16x8 hi, lo; float n[4]; };
-
-template <int MODE>
-__device__ __forceinline__ void read_frag(const char* __restrict__ tile, const float* __restrict__ ntile, int lane,
-                                          Frag<MODE>& f) {
-  if constexpr (MODE == 0) {
-    const float4* p = reinterpret_cast<const float4*>(tile + lane * 32);
-    const float4 u = p[0], w = p[1];
-    f.a[0] = u.x; f.a[1] = u.y; f.a[2] = u.z; f.a[3] = u.w;
-    f.a[4] = w.x; f.a[5] = w.y; f.a[6] = w.z; f.a[7] = w.w;
-  } else {
-    f.hi = *reinterpret_cast<const bf16x8*>(tile + lane * 16);
-    if constexpr (MODE == 2) f.lo = *reinterpret_cast<const bf16x8*>(tile + 1024 + lane * 16);
-    const float4 n = *reinterpret_cast<const float4*>(ntile + 4 * (lane >> 4));
-    f.n[0] = n.x; f.n[1] = n.y; f.n[2] = n.z; f.n[3] = n.w;
-  }
-}
-
-template <int MODE>
-struct BOp;
-template <> struct BOp<0> { float b[8]; };
-template <> struct BOp<1> { bf16x8 hi; float n; };
-template <> struct BOp<2> { bf16x8 hi, lo; float n; };
-
-template <int MODE>
-__device__ __forceinline__ void tile_dist(const Frag<MODE>& a, const BOp<MODE>& b, float (&d)[4]) {
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (MODE == 0) {
-#pragma unroll
-    for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.a[s], b.b[s], acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) d[r] = acc[r];
-  } else {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.hi, acc, 0, 0, 0);
-    if constexpr (MODE == 2) {
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.lo, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo, b.hi, acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) d[r] = (acc[r] + a.n[r]) + b.n;  // |x|^2 - 2 x.y + |y|^2
-  }
-}
-
-// Top-1 running state of a lane: per row offset r (rows 16 t + 4 g + r of its column) the
-// smallest clamped distance so far, as its f32 bit pattern (clamped values are positive, so
-// their bit patterns order as the values do), and the tile t holding it. Per distance: integer
-// max (the clamp), difference, sign mask, bit-select, integer min — no compare-to-VCC, so the
-// four chains interleave with each other and the MFMAs without hazard stalls. Ties stay with
-// the earliest tile because tiles arrive in increasing order and only a strictly smaller key
-// moves the tile.
-struct Top1x4 {
-  int k[4];
-  int t[4];
-};
-
-// The main pass, without LDS staging. Block = 4 waves = 2 column pairs x 2 row halves: wave (wc, wr) takes column tiles
-// 4 cg + 2 wc and 4 cg + 2 wc + 1 and half wr of the block's row tiles, reading the rows' MFMA
-// fragments straight from L2 into registers one chunk of CHD tiles ahead of the MFMAs (two
-// register buffers: the next chunk's loads are in flight during this chunk's 16 * CHD MFMAs).
-// Every A fragment feeds both column tiles (two independent accumulation chains per row tile,
-// half the L2 traffic per MFMA of a one-column wave); no barrier until the end, where the
-// second row half hands its lists through LDS to the first, which merges them (ties: lower
-// row) and writes the block's columns.
-template <int TOPK, int MODE>
-__global__ __launch_bounds__(64 * kWaves) void fd_main_direct_kernel(
-    const char* __restrict__ A, const char* __restrict__ Bq, const float* __restrict__ nA,
-    const float* __restrict__ nB, const int32_t* __restrict__ n1, const int32_t* __restrict__ n2, int T1, int T2,
-    int V2max, int NCG, int RS, int64_t* __restrict__ out_idx, float* __restrict__ out_dist,
-    float* __restrict__ part_v, int32_t* __restrict__ part_i) {
-  constexpr int TB = tile_bytes(MODE);
-  constexpr int CHD = MODE == 2 ? 2 : 4;
-  __shared__ float hv[2][2][16][TOPK];  // second row half's lists: [wc][column tile][column][k]
-  __shared__ int hi_[2][2][16][TOPK];
-  const int per = NCG * RS;
-  const int B = (int)(gridDim.x / per);
-  int b, k;
-  {  // all blocks of crop b on XCD b % 8 (hardware block L lands on XCD L % 8) when B % 8 == 0
-    const int L = blockIdx.x;
-    if ((B & 7) == 0) {
-      const int x8 = L & 7, q = L >> 3;
-      b = x8 + 8 * (q / per);
-      k = q - (q / per) * per;
-    } else {
-      b = L / per;
-      k = L - b * per;
-    }
-  }
-  const int cg = k % NCG, rs = k / NCG;
-  const int lane = pk::lane_id(), w = pk::wave_id();
-  const int g = lane >> 4, c16 = lane & 15;
-  // (readfirstlane: the wave-uniform values in scalar registers, so the chunk loop is a scalar
-  // loop and not an exec-masked one whose wait counts the compiler cannot track)
-  const int wc = __builtin_amdgcn_readfirstlane(w & 1), wr = __builtin_amdgcn_readfirstlane(w >> 1);
-  const int ct0 = cg * kWaves + 2 * wc;  // this wave's column tiles ct0, ct0 + 1
-  const int N1 = n1[b], N2 = n2[b];
-  const int nt = (N1 + 15) >> 4;
-  const int tb0 = (nt * rs) / RS, te0 = (nt * (rs + 1)) / RS;      // the block's row part
-  const int tb = tb0 + ((te0 - tb0) * wr) / 2, te = tb0 + ((te0 - tb0) * (wr + 1)) / 2;  // this wave's half
-  BOp<MODE> bo[2];
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {  // (a column tile past T2 reads tile T2 - 1; its lists are not written)
-    const char* bt = Bq + ((int64_t)b * T2 + min(ct0 + c, T2 - 1)) * TB;
-    if constexpr (MODE == 0) {
-      const float4* p = reinterpret_cast<const float4*>(bt + lane * 32);
-      const float4 u = p[0], v = p[1];
-      bo[c].b[0] = u.x; bo[c].b[1] = u.y; bo[c].b[2] = u.z; bo[c].b[3] = u.w;
-      bo[c].b[4] = v.x; bo[c].b[5] = v.y; bo[c].b[6] = v.z; bo[c].b[7] = v.w;
-    } else {
-      bo[c].hi = *reinterpret_cast<const bf16x8*>(bt + lane * 16);
-      if constexpr (MODE == 2) bo[c].lo = *reinterpret_cast<const bf16x8*>(bt + 1024 + lane * 16);
-      bo[c].n = nB[((int64_t)b * T2 + min(ct0 + c, T2 - 1)) * 16 + c16];
-    }
-  }
-  const char* At = A + (int64_t)b * T1 * TB;
-  const float* nAt = MODE != 0 ? nA + (int64_t)b * T1 * 16 : nullptr;
-  TopK<TOPK> best[2];
-  Top1x4 b4[2];
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    best[c].init();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      b4[c].k[r] = 0x7f800000;  // +inf: never replaced by an equal key
-      b4[c].t[r] = 0x7fffffff;
-    }
-  }
-  // tiles past te are loaded at te - 1 (unconditional loads: no branch, no early wait) and
-  // their distances masked to +inf before the selection
-  auto load = [&](Frag<MODE> (&f)[CHD], int c0) {
-#pragma unroll
-    for (int t = 0; t < CHD; ++t) {
-      const int tt = min(c0 + t, te - 1);
-      read_frag<MODE>(At + (int64_t)tt * TB, nAt ? nAt + (int64_t)tt * 16 : nullptr, lane, f[t]);
-    }
-  };
-  auto compute = [&](const Frag<MODE> (&f)[CHD], int c0) {
-#pragma unroll
-    for (int t = 0; t < CHD; ++t) {
-      float d[2][4];
-      tile_dist<MODE>(f[t], bo[0], d[0]);
-      tile_dist<MODE>(f[t], bo[1], d[1]);
-      const bool in = c0 + t < te;
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        if constexpr (TOPK == 1) {
-          constexpr int kClamp = 0x0da24260;  // bits of 1e-30f: clamp_min(1e-30) (cdist mm path)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int key = in ? max(__float_as_int(d[c][r]), kClamp) : 0x7f800000;
-            const int m = (key - b4[c].k[r]) >> 31;  // -1 iff key < best
-            b4[c].t[r] = (m & (c0 + t)) | (~m & b4[c].t[r]);
-            b4[c].k[r] = min(key, b4[c].k[r]);
-          }
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) d[c][r] = in ? d[c][r] : __builtin_huge_valf();
-          epilogue<TOPK>(d[c], (c0 + t) * 16 + 4 * g, best[c]);
-        }
-      }
-    }
-  };
-  const int nch = __builtin_amdgcn_readfirstlane(te > tb ? (te - tb + CHD - 1) / CHD : 0);
-  if (nch > 0) {
-    // (sched_barrier: the scheduler would otherwise sink each load next to its first use)
-    Frag<MODE> fa[CHD], fb[CHD];
-    load(fa, tb);
-    // (no early exit: every iteration issues both loads, so a chunk's loads are always in
-    // flight across the previous chunk's MFMAs, the back edge included)
-    for (int ci = 0; ci < nch; ci += 2) {
-      const int c0 = tb + ci * CHD;
-      load(fb, c0 + CHD);
-      __builtin_amdgcn_sched_barrier(0);
-      compute(fa, c0);
-      load(fa, c0 + 2 * CHD);
-      __builtin_amdgcn_sched_barrier(0);
-      if (ci + 1 < nch) compute(fb, c0 + CHD);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    if constexpr (TOPK == 1) {  // the 4 row offsets: smallest value, ties lowest row
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = b4[c].t[r] == 0x7fffffff ? 0x7fffffff : b4[c].t[r] * 16 + 4 * g + r;
-        const float v = __int_as_float(b4[c].k[r]);
-        const bool take = v < best[c].v[0] || (v == best[c].v[0] && row < best[c].i[0]);
-        best[c].v[0] = take ? v : best[c].v[0];
-        best[c].i[0] = take ? row : best[c].i[0];
-      }
-    }
-    lanegroup_merge<TOPK>(best[c]);
-  }
-  // the second row half's lists to the first (ties: lower row — the merge's index rule)
-  if (wr == 1 && g == 0) {
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int q = 0; q < TOPK; ++q) {
-        hv[wc][c][c16][q] = best[c].v[q];
-        hi_[wc][c][c16][q] = best[c].i[q];
-      }
-  }
-  __syncthreads();
-  if (wr == 1 || g != 0) return;
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    float ov[TOPK];
-    int oi[TOPK];
-#pragma unroll
-    for (int q = 0; q < TOPK; ++q) {
-      ov[q] = hv[wc][c][c16][q];
-      oi[q] = hi_[wc][c][c16][q];
-    }
-    best[c].merge(ov, oi);
-    const int ct = ct0 + c;
-    const int j = ct * 16 + c16;
-    if (ct >= T2 || j >= N2) continue;
-    if (RS == 1) {
-      const int64_t o = ((int64_t)b * V2max + j) * TOPK;
-#pragma unroll
-      for (int q = 0; q < TOPK; ++q) {
-        out_idx[o + q] = best[c].i[q] == 0x7fffffff ? -1 : best[c].i[q];
-        if (out_dist) out_dist[o + q] = sqrtf(best[c].v[q]);
-      }
-    } else {
-      const int64_t o = (((int64_t)b * RS + rs) * V2max + j) * TOPK;
-#pragma unroll
-      for (int q = 0; q < TOPK; ++q) {
-        part_v[o + q] = best[c].v[q];
-        part_i[o + q] = best[c].i[q];
-      }
-    }
-  }
-}
 
 // Top-1 fp32 (round 5, the default argmin of the training step's naive point map and the IR):
 // nothing kept across calls (no arrival words, no zeroing contract on `work`).
@@ -576,17 +123,7 @@ __global__ __launch_bounds__(512) void fd_top1_prep_kernel(const float* __restri
   const int g = lane >> 4, c16 = lane & 15;
   const int B = (int)(gridDim.x / NTG);
   int b, tg;
-  {
-    const int L = blockIdx.x;
-    if ((B & 7) == 0) {
-      const int x8 = L & 7, q = L >> 3;
-      b = x8 + 8 * (q / NTG);
-      tg = q - (q / NTG) * NTG;
-    } else {
-      b = L / NTG;
-      tg = L - b * NTG;
-    }
-  }
+  fd_crop_block(NTG, B, b, tg);
   const int t = tg * 8 + w;
   const int N1 = n1[b];
   const bool act = t < T1 && t * 16 < N1;
@@ -632,95 +169,158 @@ __global__ __launch_bounds__(512) void fd_top1_prep_kernel(const float* __restri
   asm volatile("" ::"v"(yt[0]), "v"(yt[1]), "v"(yt[2]), "v"(yt[3]));  // (keeps the touch loads)
 }
 
-// pass 2 (ex, ldx and C are not read: the row operands come from pass 1's tiles)
+// ---- the layout that pass 2 of the argmin (fd_top1_kernel) and of the top-5 (fd_top5_kernel) share
+
+// this wave's row tiles [tb, te) of the crop's nt: wave w of the 8 of row part rs of RS
+__device__ __forceinline__ void top1_wave_tiles(int nt, int RS, int rs, int w, int& tb, int& te) {
+  const int Q = RS * kTop1Waves, qw = rs * kTop1Waves + w;
+  tb = (int)((int64_t)nt * qw / Q);
+  te = (int)((int64_t)nt * (qw + 1) / Q);
+}
+
+// the operand of tile t: pass 1's A tile (two 16-B loads per lane)
+__device__ __forceinline__ void top1_opload(const f32x4* __restrict__ Ab, int t, int lane, float4 (&xv)[2]) {
+  const f32x4 u0 = Ab[(int64_t)t * 128 + lane], u1 = Ab[(int64_t)t * 128 + 64 + lane];
+  xv[0] = make_float4(u0[0], u0[1], u0[2], u0[3]);
+  xv[1] = make_float4(u1[0], u1[1], u1[2], u1[3]);
+}
+
+__device__ __forceinline__ void top1_unpack(const float4 (&xv)[2], float (&a)[8]) {
+  a[0] = xv[0].x, a[1] = xv[0].y, a[2] = xv[0].z, a[3] = xv[0].w;
+  a[4] = xv[1].x, a[5] = xv[1].y, a[6] = xv[1].z, a[7] = xv[1].w;
+}
+
+// Column staging: the block's 128 columns' [y, 1, |y|^2] in B order, through LDS into every wave's
+// registers. Thread tid stages column jj of the block for lane group gy.
+struct Top1Col {
+  int jj, gy;
+  float4 y0, y1;
+};
+
+// the staging thread's loads; they go out beside the crop sizes' (their addresses do not need them)
+__device__ __forceinline__ Top1Col top1_col_load(const float* __restrict__ ey, int ldy, int b, int V2max, int j0,
+                                                 int tid) {
+  Top1Col s;
+  s.jj = tid & (kTop1CT * 16 - 1);
+  s.gy = tid >> 7;
+  const float* syr = ey + ((int64_t)b * V2max + min(j0 + s.jj, V2max - 1)) * ldy;
+  s.y0 = *reinterpret_cast<const float4*>(syr + 4 * s.gy);
+  s.y1 = *reinterpret_cast<const float4*>(syr + 16 + 4 * s.gy);
+  return s;
+}
+
+// The staging has two halves around its first barrier; between them a kernel leaves if the block
+// lies past its crop's columns (j0 >= N2, block-uniform: after the loads' consumers, so they are
+// not sunk past the return) and does what need not wait for the staging while the partials meet.
+// First half: v = the thread's 8 values (zeros past the crop's columns and past the 30 features),
+// their partial |y|^2 to sPart.
+__device__ __forceinline__ void top1_stage_partials(const Top1Col& s, int j0, int N2, float (*sPart)[kTop1CT * 16],
+                                                    float (&v)[8]) {
+  const bool ok = j0 + s.jj < N2;
+  v[0] = s.y0.x, v[1] = s.y0.y, v[2] = s.y0.z, v[3] = s.y0.w;
+  v[4] = s.y1.x, v[5] = s.y1.y, v[6] = s.y1.z, v[7] = s.y1.w;
+  float part_ = 0.f;
+#pragma unroll
+  for (int s8 = 0; s8 < 8; ++s8) {
+    v[s8] = (ok && (s8 < 6 || s.gy < 3)) ? v[s8] : 0.f;
+    part_ = fmaf(v[s8], v[s8], part_);
+  }
+  sPart[s.gy][s.jj] = part_;
+}
+
+// Second half, from the barrier on the partials: bo[c][s] = this lane's B operands of column tile c.
+__device__ __forceinline__ void top1_stage_operands(const Top1Col& s, float (&v)[8], int lane,
+                                                    float (*sPart)[kTop1CT * 16], f32x4 (*sB)[2][64],
+                                                    float (&bo)[kTop1CT][8]) {
+  const int jj = s.jj, gy = s.gy;
+  __syncthreads();
+  if (gy == 3) {  // |y|^2: the lane groups' partials in the order 0, 1, 2, 3
+    float nrm = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) nrm += sPart[q][jj];
+    v[6] = 1.f;
+    v[7] = nrm;
+  }
+  const int c = jj >> 4, l = gy * 16 + (jj & 15);
+  sB[c][0][l] = f32x4{v[0], v[1], v[2], v[3]};
+  sB[c][1][l] = f32x4{v[4], v[5], v[6], v[7]};
+  __syncthreads();
+#pragma unroll
+  for (int c2 = 0; c2 < kTop1CT; ++c2)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const f32x4 t4 = sB[c2][h][lane];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) bo[c2][4 * h + q] = t4[q];
+    }
+}
+
+// The tile loop, software-pipelined: tile t's 8 column tiles in pairs (two accumulation chains
+// each), the selection sel(acc, column tile, t) of pair p - 1 behind pair p's MFMAs, tile t + 1's
+// operand (xn, loaded two tiles ahead) behind the last pair; no branch in the body (loads past the
+// wave's last tile re-read its last tile, never used). On entry a holds tile tb's operand and xn
+// tile tb + 1's.
+template <class Sel>
+__device__ __forceinline__ void top1_tile_loop(const f32x4* __restrict__ Ab, int lane, int tb, int te,
+                                               const float (&bo)[kTop1CT][8], float (&a)[8], float4 (&xn)[2],
+                                               Sel sel) {
+  for (int t = tb; t < te; ++t) {
+    f32x4 acc[kTop1CT];
+#pragma unroll
+    for (int p = 0; p < kTop1CT / 2; ++p) {
+      f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], bo[2 * p][s], a0, 0, 0, 0);
+        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], bo[2 * p + 1][s], a1, 0, 0, 0);
+      }
+      acc[2 * p] = a0;
+      acc[2 * p + 1] = a1;
+      if (p > 0) {
+        sel(acc[2 * p - 2], 2 * p - 2, t);
+        sel(acc[2 * p - 1], 2 * p - 1, t);
+      }
+    }
+    top1_unpack(xn, a);
+    top1_opload(Ab, min(t + 2, te - 1), lane, xn);
+    sel(acc[kTop1CT - 2], kTop1CT - 2, t);
+    sel(acc[kTop1CT - 1], kTop1CT - 1, t);
+  }
+}
+
+// pass 2 (the row operands come from pass 1's tiles)
 __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top1_kernel(
-    const float* __restrict__ ex, int ldx, const float* __restrict__ C, const f32x4* __restrict__ Atile, int T1,
-    const float* __restrict__ ey, int ldy, const int32_t* __restrict__ n1, const int32_t* __restrict__ n2, int V1max,
-    int V2max, int NCG, int RS, int64_t* __restrict__ out_idx, float* __restrict__ out_dist,
-    unsigned long long* __restrict__ part) {
+    const f32x4* __restrict__ Atile, int T1, const float* __restrict__ ey, int ldy, const int32_t* __restrict__ n1,
+    const int32_t* __restrict__ n2, int V2max, int NCG, int RS, int64_t* __restrict__ out_idx,
+    float* __restrict__ out_dist, unsigned long long* __restrict__ part) {
   __shared__ f32x4 sB[kTop1CT][2][64];      // the column operands in B order (16 KB)
   __shared__ float sPart[4][kTop1CT * 16];  // per lane group partial |y|^2
   __shared__ unsigned long long wkeys[kTop1Waves][kTop1CT * 16];
   const int per = NCG * RS;
   const int B = (int)(gridDim.x / per);
   int b, k;
-  {  // all blocks of crop b on XCD b % 8 (hardware block L lands on XCD L % 8) when B % 8 == 0
-    const int L = blockIdx.x;
-    if ((B & 7) == 0) {
-      const int x8 = L & 7, q = L >> 3;
-      b = x8 + 8 * (q / per);
-      k = q - (q / per) * per;
-    } else {
-      b = L / per;
-      k = L - b * per;
-    }
-  }
+  fd_crop_block(per, B, b, k);
   const int cg = k % NCG, rs = k / NCG;
   const int j0 = cg * kTop1CT * 16;
   const int tid = threadIdx.x, lane = pk::lane_id(), w = __builtin_amdgcn_readfirstlane(pk::wave_id());
-  // the column operands' loads go out beside the crop sizes' (their addresses do not need them)
-  const int sjj = tid & (kTop1CT * 16 - 1), sgy = tid >> 7;  // staging: column sjj, lane group sgy
-  const float* syr = ey + ((int64_t)b * V2max + min(j0 + sjj, V2max - 1)) * ldy;
-  const float4 sy0 = *reinterpret_cast<const float4*>(syr + 4 * sgy);
-  const float4 sy1 = *reinterpret_cast<const float4*>(syr + 16 + 4 * sgy);
+  const Top1Col sc = top1_col_load(ey, ldy, b, V2max, j0, tid);
   const int N1 = n1[b], N2 = n2[b];
   const int g = lane >> 4, c16 = lane & 15;
   const int nt = (N1 + 15) >> 4;
-  const int Q = RS * kTop1Waves, qw = rs * kTop1Waves + w;
-  const int tb = (int)((int64_t)nt * qw / Q), te = (int)((int64_t)nt * (qw + 1) / Q);  // this wave's row tiles
+  int tb, te;
+  top1_wave_tiles(nt, RS, rs, w, tb, te);
   const f32x4* Ab = Atile + (int64_t)b * T1 * 128;
-  // the operand of tile t: pass 1's A tile (two 16-B loads per lane)
-  auto opload = [&](int t, float4 (&xv)[2]) {
-    const f32x4 u0 = Ab[(int64_t)t * 128 + lane], u1 = Ab[(int64_t)t * 128 + 64 + lane];
-    xv[0] = make_float4(u0[0], u0[1], u0[2], u0[3]);
-    xv[1] = make_float4(u1[0], u1[1], u1[2], u1[3]);
-  };
-  auto unpack = [](const float4 (&xv)[2], float (&a)[8]) {
-    a[0] = xv[0].x, a[1] = xv[0].y, a[2] = xv[0].z, a[3] = xv[0].w;
-    a[4] = xv[1].x, a[5] = xv[1].y, a[6] = xv[1].z, a[7] = xv[1].w;
-  };
   float4 xc[2], xn[2];
   float a[8];
   if (tb < te) {
-    opload(tb, xc);
-    opload(min(tb + 1, te - 1), xn);
+    top1_opload(Ab, tb, lane, xc);
+    top1_opload(Ab, min(tb + 1, te - 1), lane, xn);
   }
-  float bo[kTop1CT][8];
-  {  // staging: the block's 128 columns' [y, 1, |y|^2] in B order, through LDS
-    const int jj = sjj, gy = sgy;  // column jj of the block, lane group gy
-    const int j = j0 + jj;
-    const bool ok = j < N2;
-    float v[8] = {sy0.x, sy0.y, sy0.z, sy0.w, sy1.x, sy1.y, sy1.z, sy1.w};
-    float part_ = 0.f;
-#pragma unroll
-    for (int s8 = 0; s8 < 8; ++s8) {
-      v[s8] = (ok && (s8 < 6 || gy < 3)) ? v[s8] : 0.f;
-      part_ = fmaf(v[s8], v[s8], part_);
-    }
-    sPart[gy][jj] = part_;
-    if (j0 >= N2) return;  // (block-uniform; after the loads' consumers, so they are not sunk past it)
-    if (tb < te) unpack(xc, a);  // (the first tile's operand while the partials meet)
-    __syncthreads();
-    if (gy == 3) {  // |y|^2: the lane groups' partials in the order 0, 1, 2, 3
-      float nrm = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) nrm += sPart[q][jj];
-      v[6] = 1.f;
-      v[7] = nrm;
-    }
-    const int c = jj >> 4, l = gy * 16 + (jj & 15);
-    sB[c][0][l] = f32x4{v[0], v[1], v[2], v[3]};
-    sB[c][1][l] = f32x4{v[4], v[5], v[6], v[7]};
-    __syncthreads();
-#pragma unroll
-    for (int c2 = 0; c2 < kTop1CT; ++c2)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const f32x4 t4 = sB[c2][h][lane];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) bo[c2][4 * h + q] = t4[q];
-      }
-  }
+  float bo[kTop1CT][8], sv[8];
+  top1_stage_partials(sc, j0, N2, sPart, sv);
+  if (j0 >= N2) return;
+  if (tb < te) top1_unpack(xc, a);  // (the first tile's operand while the partials meet)
+  top1_stage_operands(sc, sv, lane, sPart, sB, bo);
   int bk[kTop1CT][4], bt[kTop1CT][4];
 #pragma unroll
   for (int c = 0; c < kTop1CT; ++c)
@@ -751,32 +351,7 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top1_kernel(
         : [k0] "v"(__float_as_int(acc[0])), [k1] "v"(__float_as_int(acc[1])), [k2] "v"(__float_as_int(acc[2])),
           [k3] "v"(__float_as_int(acc[3])), [tv] "v"(t));
   };
-  // software pipeline: tile t's 8 column tiles in pairs (two accumulation chains each), the
-  // selection of pair p - 1 behind pair p's MFMAs, tile t + 1's operand (loaded two tiles ahead)
-  // behind the last pair; no branch in the body (loads past the wave's last tile re-read its last
-  // tile, never used)
-  for (int t = tb; t < te; ++t) {
-    f32x4 acc[kTop1CT];
-#pragma unroll
-    for (int p = 0; p < kTop1CT / 2; ++p) {
-      f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], bo[2 * p][s], a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], bo[2 * p + 1][s], a1, 0, 0, 0);
-      }
-      acc[2 * p] = a0;
-      acc[2 * p + 1] = a1;
-      if (p > 0) {
-        sel(acc[2 * p - 2], 2 * p - 2, t);
-        sel(acc[2 * p - 1], 2 * p - 1, t);
-      }
-    }
-    unpack(xn, a);
-    opload(min(t + 2, te - 1), xn);
-    sel(acc[kTop1CT - 2], kTop1CT - 2, t);
-    sel(acc[kTop1CT - 1], kTop1CT - 1, t);
-  }
+  top1_tile_loop(Ab, lane, tb, te, bo, a, xn, sel);
   // per column tile: the lane's best (value, row) over its 4 row offsets: the smallest key, then
   // the lowest row holding it
   int bv[kTop1CT];
@@ -800,9 +375,9 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top1_kernel(
       unsigned frow = 0x7fffffffu;
       for (int t = tb; t < te; ++t) {
         float4 xv[2];
-        opload(t, xv);
+        top1_opload(Ab, t, lane, xv);
         float at[8];
-        unpack(xv, at);
+        top1_unpack(xv, at);
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(at[s], bo[c][s], acc, 0, 0, 0);
@@ -878,8 +453,9 @@ __global__ __launch_bounds__(256) void fd_top1_merge_kernel(const unsigned long 
 // ---------------------------------------------------------------------------------------------
 // Top-5 fp32 (round 6): the configured solver's candidates, nn_query's dist.sort(dim=-2)[1].T[:, :5]
 // (spacial_filtering.py:32-38; config/dpfm_orig.gin:71). Pass 1 is fd_top1_prep_kernel. Pass 2,
-// fd_top5_kernel, keeps fd_top1_kernel's layout (block = crop b x 128 columns x row part rs, 8 waves
-// splitting the row tiles, the columns' B operands in registers) and its selection cost: on gfx950
+// fd_top5_kernel, has fd_top1_kernel's layout (block = crop b x 128 columns x row part rs, 8 waves
+// splitting the row tiles, the columns' B operands in registers: the shared pieces above, the tile
+// loop among them) and its selection cost: on gfx950
 // the f32 MFMAs and the VALU issue one after the other (tools/mfma_valu_probe.py: every VALU op
 // adds its issue cycles to the MFMA time), so the per-distance work is 4 instructions. Per STREAM =
 // (column tile c, row offset r) of a lane — rows 16 t + 4 g + r of its column over the wave's
@@ -978,91 +554,38 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
   const int per = NCG * RS;
   const int B = (int)(gridDim.x / per);
   int b, k;
-  {  // all blocks of crop b on XCD b % 8 when B % 8 == 0 (as fd_top1_kernel)
-    const int L = blockIdx.x;
-    if ((B & 7) == 0) {
-      const int x8 = L & 7, q = L >> 3;
-      b = x8 + 8 * (q / per);
-      k = q - (q / per) * per;
-    } else {
-      b = L / per;
-      k = L - b * per;
-    }
-  }
+  fd_crop_block(per, B, b, k);
   const int cg = k % NCG, rs = k / NCG;
   const int j0 = cg * NC;
   const int tid = threadIdx.x, lane = pk::lane_id(), w = __builtin_amdgcn_readfirstlane(pk::wave_id());
-  // the column operands' loads go out beside the crop sizes' (as fd_top1_kernel)
-  const int sjj = tid & (NC - 1), sgy = tid >> 7;
-  const float* syr = ey + ((int64_t)b * V2max + min(j0 + sjj, V2max - 1)) * ldy;
-  const float4 sy0 = *reinterpret_cast<const float4*>(syr + 4 * sgy);
-  const float4 sy1 = *reinterpret_cast<const float4*>(syr + 16 + 4 * sgy);
+  const Top1Col sc = top1_col_load(ey, ldy, b, V2max, j0, tid);
   const int N1 = n1[b], N2 = n2[b];
   const int g = lane >> 4, c16 = lane & 15;
   const int nt = (N1 + 15) >> 4;
-  const int Q = RS * kTop1Waves;
-  const int qw = rs * kTop1Waves + w;
-  const int tb = (int)((int64_t)nt * qw / Q), te = (int)((int64_t)nt * (qw + 1) / Q);  // this wave's row tiles
+  int tb, te;
+  top1_wave_tiles(nt, RS, rs, w, tb, te);
   const f32x4* Ab = Atile + (int64_t)b * T1 * 128;
-  auto opload = [&](int t, float4 (&xv)[2]) {
-    const f32x4 u0 = Ab[(int64_t)t * 128 + lane], u1 = Ab[(int64_t)t * 128 + 64 + lane];
-    xv[0] = make_float4(u0[0], u0[1], u0[2], u0[3]);
-    xv[1] = make_float4(u1[0], u1[1], u1[2], u1[3]);
-  };
   float4 xc[2], xn[2];
   float a[8];
   if (tb < te) {
-    opload(tb, xc);
-    opload(min(tb + 1, te - 1), xn);
+    top1_opload(Ab, tb, lane, xc);
+    top1_opload(Ab, min(tb + 1, te - 1), lane, xn);
   }
-  float bo[kTop1CT][8];
-  {  // staging: the block's 128 columns' [y, 1, |y|^2] in B order, through LDS (as fd_top1_kernel)
-    const int jj = sjj, gy = sgy;
-    const int j = j0 + jj;
-    const bool ok = j < N2;
-    float v[8] = {sy0.x, sy0.y, sy0.z, sy0.w, sy1.x, sy1.y, sy1.z, sy1.w};
-    float part_ = 0.f;
-#pragma unroll
-    for (int s8 = 0; s8 < 8; ++s8) {
-      v[s8] = (ok && (s8 < 6 || gy < 3)) ? v[s8] : 0.f;
-      part_ = fmaf(v[s8], v[s8], part_);
-    }
-    sPart[gy][jj] = part_;
-    if (j0 >= N2) return;  // (block-uniform; after the loads' consumers)
-    if (tb < te) {
-      a[0] = xc[0].x, a[1] = xc[0].y, a[2] = xc[0].z, a[3] = xc[0].w;
-      a[4] = xc[1].x, a[5] = xc[1].y, a[6] = xc[1].z, a[7] = xc[1].w;
-    }
-    if (tid < NC) sCnt[tid] = 0;
-    if (lane == 0) {  // the waves' row-tile ranges (E3's task listing reads them)
-      sTR[w][0] = tb;
-      sTR[w][1] = te;
-    }
-    if (tid == 0) {
-      sNslow = 0;
-      sNtask = 0;
-    }
-    __syncthreads();
-    if (gy == 3) {
-      float nrm = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) nrm += sPart[q][jj];
-      v[6] = 1.f;
-      v[7] = nrm;
-    }
-    const int c = jj >> 4, l = gy * 16 + (jj & 15);
-    sB[c][0][l] = f32x4{v[0], v[1], v[2], v[3]};
-    sB[c][1][l] = f32x4{v[4], v[5], v[6], v[7]};
-    __syncthreads();
-#pragma unroll
-    for (int c2 = 0; c2 < kTop1CT; ++c2)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const f32x4 t4 = sB[c2][h][lane];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) bo[c2][4 * h + q] = t4[q];
-      }
+  float bo[kTop1CT][8], sv[8];
+  top1_stage_partials(sc, j0, N2, sPart, sv);
+  if (j0 >= N2) return;
+  // the first tile's operand and the selection's LDS state, while the partials meet
+  if (tb < te) top1_unpack(xc, a);
+  if (tid < NC) sCnt[tid] = 0;
+  if (lane == 0) {  // the waves' row-tile ranges (E3's task listing reads them)
+    sTR[w][0] = tb;
+    sTR[w][1] = te;
   }
+  if (tid == 0) {
+    sNslow = 0;
+    sNtask = 0;
+  }
+  top1_stage_operands(sc, sv, lane, sPart, sB, bo);
   int k1[kTop1CT][4], t1[kTop1CT][4], k2[kTop1CT][4];
 #pragma unroll
   for (int c = 0; c < kTop1CT; ++c)
@@ -1098,29 +621,7 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
         : [k0] "v"(__float_as_int(acc[0])), [k1] "v"(__float_as_int(acc[1])), [k2] "v"(__float_as_int(acc[2])),
           [k3] "v"(__float_as_int(acc[3])), [tv] "v"(t));
   };
-  for (int t = tb; t < te; ++t) {  // (the top-1 pass's software pipeline)
-    f32x4 acc[kTop1CT];
-#pragma unroll
-    for (int p = 0; p < kTop1CT / 2; ++p) {
-      f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], bo[2 * p][s], a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], bo[2 * p + 1][s], a1, 0, 0, 0);
-      }
-      acc[2 * p] = a0;
-      acc[2 * p + 1] = a1;
-      if (p > 0) {
-        sel(acc[2 * p - 2], 2 * p - 2, t);
-        sel(acc[2 * p - 1], 2 * p - 1, t);
-      }
-    }
-    a[0] = xn[0].x, a[1] = xn[0].y, a[2] = xn[0].z, a[3] = xn[0].w;
-    a[4] = xn[1].x, a[5] = xn[1].y, a[6] = xn[1].z, a[7] = xn[1].w;
-    opload(min(t + 2, te - 1), xn);
-    sel(acc[kTop1CT - 2], kTop1CT - 2, t);
-    sel(acc[kTop1CT - 1], kTop1CT - 1, t);
-  }
+  top1_tile_loop(Ab, lane, tb, te, bo, a, xn, sel);
   // E0: the lane minima (over r) of every column, per (wave, lane group)
 #pragma unroll
   for (int c = 0; c < kTop1CT; ++c)
@@ -1336,7 +837,9 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
   __syncthreads();
   // slow path: one wave per column, every row of this row part, clamped distances, lower row first
   const int nslow = sNslow;
-  const int pt0 = (int)((int64_t)nt * (rs * kTop1Waves) / Q), pt1 = (int)((int64_t)nt * (rs * kTop1Waves + kTop1Waves) / Q);
+  int pt0, pt1, unused;  // the row part's tiles: from its first wave's first to its last wave's last
+  top1_wave_tiles(nt, RS, rs, 0, pt0, unused);
+  top1_wave_tiles(nt, RS, rs, kTop1Waves - 1, unused, pt1);
   for (int si = w; si < nslow; si += kTop1Waves) {
     const int col = sSlow[si];
     unsigned long long bl[5];
@@ -1363,14 +866,15 @@ __global__ __launch_bounds__(64 * kTop1Waves, 1) void fd_top5_kernel(
   }
 }
 
+// The one-pass path's launch geometry and scratch: the A tiles, then (RS > 1) the row parts'
+// results: the argmin's keys (part_bytes), or the top-5's values and then indices (t5_bytes each).
 struct Top1Plan {
   int T1, T2, NCG, RS;
-  int64_t a_bytes, b_bytes, part_bytes;
+  int64_t a_bytes, part_bytes, t5_bytes;
 };
 
-inline int64_t al256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
 inline Top1Plan top1_plan(int B, int V1max, int V2max) {
+  using pk::al256;
   Top1Plan p{};
   const int T1 = (V1max + 15) / 16, T2 = (V2max + 15) / 16;
   p.NCG = std::max(1, (T2 + kTop1CT - 1) / kTop1CT);
@@ -1381,63 +885,8 @@ inline Top1Plan top1_plan(int B, int V1max, int V2max) {
   p.T1 = T1;
   p.T2 = T2;
   p.a_bytes = al256((int64_t)B * T1 * 2048);
-  p.b_bytes = al256((int64_t)B * T2 * 2048);
   p.part_bytes = p.RS > 1 ? al256((int64_t)B * p.RS * V2max * 8) : 0;
-  return p;
-}
-
-// pass 3 (RS > 1): grid (ceil(V2max / 256), B): merge the RS partial lists of each column in
-// row-split order (ties: lower row).
-template <int TOPK>
-__global__ __launch_bounds__(256) void fd_merge_kernel(const float* __restrict__ part_v,
-                                                       const int32_t* __restrict__ part_i,
-                                                       const int32_t* __restrict__ n2, int V2max, int RS,
-                                                       int64_t* __restrict__ out_idx, float* __restrict__ out_dist) {
-  const int b = blockIdx.y;
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n2[b]) return;
-  TopK<TOPK> best;
-  best.init();
-  for (int rs = 0; rs < RS; ++rs) {
-    const int64_t o = (((int64_t)b * RS + rs) * V2max + j) * TOPK;
-    float ov[TOPK];
-    int oi[TOPK];
-#pragma unroll
-    for (int q = 0; q < TOPK; ++q) {
-      ov[q] = part_v[o + q];
-      oi[q] = part_i[o + q];
-    }
-    best.merge(ov, oi);
-  }
-  const int64_t o = ((int64_t)b * V2max + j) * TOPK;
-#pragma unroll
-  for (int q = 0; q < TOPK; ++q) {
-    out_idx[o + q] = best.i[q] == 0x7fffffff ? -1 : best.i[q];
-    if (out_dist) out_dist[o + q] = sqrtf(best.v[q]);
-  }
-}
-
-struct FdPlan {
-  int T1, T2, NCG, RS;
-  int64_t a_bytes, b_bytes, na_bytes, nb_bytes, pv_bytes, pi_bytes;
-};
-
-inline FdPlan fd_plan(int B, int V1max, int V2max, int topk, int mode) {
-  FdPlan p{};
-  p.T1 = (V1max + 15) / 16;
-  p.T2 = (V2max + 15) / 16;
-  p.NCG = (p.T2 + kWaves * kCW - 1) / (kWaves * kCW);
-  const int64_t blocks = (int64_t)B * p.NCG;
-  int rs = blocks >= 512 ? 1 : (int)((512 + blocks - 1) / blocks);
-  const int max_rs = std::max(1, p.T1 / (2 * kCH));  // at least two chunks per row part
-  p.RS = std::min(rs, max_rs);
-  const int TB = tile_bytes(mode);
-  p.a_bytes = al256((int64_t)B * p.T1 * TB);
-  p.b_bytes = al256((int64_t)B * p.T2 * TB);
-  p.na_bytes = mode ? al256((int64_t)B * p.T1 * 16 * 4) : 0;
-  p.nb_bytes = mode ? al256((int64_t)B * p.T2 * 16 * 4) : 0;
-  p.pv_bytes = p.RS > 1 ? al256((int64_t)B * p.RS * V2max * topk * 4) : 0;
-  p.pi_bytes = p.pv_bytes;
+  p.t5_bytes = p.RS > 1 ? al256((int64_t)B * p.RS * V2max * 5 * 4) : 0;
   return p;
 }
 
@@ -1446,14 +895,12 @@ inline FdPlan fd_plan(int B, int V1max, int V2max, int topk, int mode) {
 extern "C" int64_t pk_feat_dist_work_size(int B, int V1max, int V2max, int topk, int mode) {
   if (B < 0 || V1max < 0 || V2max < 0 || !(topk == 1 || topk == 5) || mode < 0 || mode > 2) return -1;
   if (mode == 0 && topk == 5 && V1max > kT5MaxRows) return -1;
-  const FdPlan p = fd_plan(B, V1max, V2max, topk, mode);
-  const int64_t two_pass = p.a_bytes + p.b_bytes + p.na_bytes + p.nb_bytes + p.pv_bytes + p.pi_bytes;
+  const int64_t two_pass = pk::fd_twopass_work_size(B, V1max, V2max, topk, mode);
   if (mode != 0) return two_pass;
   // mode 0: the prep + main pass's operand tiles and row-part keys (top-1) / lists (top-5), or the
   // two-pass fallback's scratch (unaligned operand rows); none keeps anything across calls
   const Top1Plan tp = top1_plan(B, V1max, V2max);
-  const int64_t t5parts = tp.RS > 1 ? 2 * al256((int64_t)B * tp.RS * V2max * 5 * 4) : 0;
-  return std::max(two_pass, tp.a_bytes + (topk == 1 ? tp.part_bytes : t5parts));
+  return std::max(two_pass, tp.a_bytes + (topk == 1 ? tp.part_bytes : 2 * tp.t5_bytes));
 }
 
 extern "C" int pk_feat_dist_topk(const float* evecs_x, int ldx, const float* C, const float* evecs_y, int ldy,
@@ -1470,77 +917,36 @@ extern "C" int pk_feat_dist_topk(const float* evecs_x, int ldx, const float* C, 
   hipStream_t s = pk::as_stream(stream);
   const bool aligned = (ldx % 4) == 0 && (ldy % 4) == 0 && (reinterpret_cast<uintptr_t>(evecs_x) & 15) == 0 &&
                        (reinterpret_cast<uintptr_t>(evecs_y) & 15) == 0;
-  if (mode == 0 && aligned && V1max > 0 && topk == 5) {  // prep + main (+ merge when RS > 1)
-    const Top1Plan tp = top1_plan(B, V1max, V2max);
-    auto* At = static_cast<f32x4*>(work);
-    float* pv = tp.RS > 1 ? reinterpret_cast<float*>(static_cast<char*>(work) + tp.a_bytes) : nullptr;
-    int32_t* pi = tp.RS > 1 ? reinterpret_cast<int32_t*>(reinterpret_cast<char*>(pv) +
-                                                         al256((int64_t)B * tp.RS * V2max * 5 * 4))
-                            : nullptr;
-    hipLaunchKernelGGL(fd_top1_prep_kernel, dim3((unsigned)(((tp.T1 + 7) / 8) * B)), dim3(512), 0, s, evecs_x, ldx, C,
-                       n1, V1max, tp.T1, At, evecs_y, ldy, n2, V2max, (tp.T1 + 7) / 8);
-    PK_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fd_top5_kernel, dim3((unsigned)((int64_t)B * tp.NCG * tp.RS)), dim3(64 * kTop1Waves), 0, s, At,
-                       tp.T1, evecs_y, ldy, n1, n2, V2max, tp.NCG, tp.RS, out_idx, out_dist, pv, pi);
-    PK_CHECK_LAUNCH();
-    if (tp.RS > 1) {
-      hipLaunchKernelGGL(fd_merge_kernel<5>, dim3((V2max + 255) / 256, B), dim3(256), 0, s, pv, pi, n2, V2max, tp.RS,
-                         out_idx, out_dist);
-      PK_CHECK_LAUNCH();
-    }
-    return PK_OK;
-  }
-  if (mode == 0 && aligned && V1max > 0 && topk == 1) {  // two launches (+ a merge launch when RS > 1)
-    const Top1Plan tp = top1_plan(B, V1max, V2max);
-    auto* At = static_cast<f32x4*>(work);
-    auto* part = reinterpret_cast<unsigned long long*>(static_cast<char*>(work) + tp.a_bytes);
-    const dim3 grid((unsigned)((int64_t)B * tp.NCG * tp.RS));
-    hipLaunchKernelGGL(fd_top1_prep_kernel, dim3((unsigned)(((tp.T1 + 7) / 8) * B)), dim3(512), 0, s, evecs_x, ldx, C,
-                       n1, V1max, tp.T1, At, evecs_y, ldy, n2, V2max, (tp.T1 + 7) / 8);
-    PK_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fd_top1_kernel, grid, dim3(64 * kTop1Waves), 0, s, evecs_x, ldx, C, At, tp.T1, evecs_y, ldy, n1,
-                       n2, V1max, V2max, tp.NCG, tp.RS, out_idx, out_dist, part);
-    PK_CHECK_LAUNCH();
-    if (tp.RS > 1) {
-      hipLaunchKernelGGL(fd_top1_merge_kernel, dim3((V2max + 255) / 256, B), dim3(256), 0, s, part, n2, V2max, tp.RS,
-                         out_idx, out_dist);
-      PK_CHECK_LAUNCH();
-    }
-    return PK_OK;
-  }
-  const FdPlan p = fd_plan(B, V1max, V2max, topk, mode);
-  char* wp = static_cast<char*>(work);
-  char* A = wp;
-  char* Bq = A + p.a_bytes;
-  float* nA = mode ? reinterpret_cast<float*>(Bq + p.b_bytes) : nullptr;
-  float* nB = mode ? reinterpret_cast<float*>(Bq + p.b_bytes + p.na_bytes) : nullptr;
-  float* pv = p.RS > 1 ? reinterpret_cast<float*>(Bq + p.b_bytes + p.na_bytes + p.nb_bytes) : nullptr;
-  int32_t* pi = p.RS > 1 ? reinterpret_cast<int32_t*>(reinterpret_cast<char*>(pv) + p.pv_bytes) : nullptr;
-  const dim3 pg((std::max(p.T1, p.T2) + kPrepWaves - 1) / kPrepWaves, B, 2);
-#define PK_FD_PREP(M)                                                                                              \
-  hipLaunchKernelGGL((fd_prep_kernel<M>), pg, dim3(64 * kPrepWaves), 0, s, evecs_x, ldx, C, evecs_y, ldy, n1, n2, V1max, V2max, \
-                     p.T1, p.T2, A, Bq, nA, nB)
-  if (mode == 0) PK_FD_PREP(0); else if (mode == 1) PK_FD_PREP(1); else PK_FD_PREP(2);
-#undef PK_FD_PREP
+  if (!(mode == 0 && aligned && V1max > 0))
+    return pk::fd_twopass_launch(evecs_x, ldx, C, evecs_y, ldy, n1, n2, B, V1max, V2max, topk, mode, work, out_idx,
+                                 out_dist, s);
+  // the one-pass path: prep + main (+ a merge launch when RS > 1)
+  const Top1Plan tp = top1_plan(B, V1max, V2max);
+  auto* At = static_cast<f32x4*>(work);
+  char* parts = static_cast<char*>(work) + tp.a_bytes;  // the row parts' results (RS > 1)
+  const dim3 grid((unsigned)((int64_t)B * tp.NCG * tp.RS)), mg((V2max + 255) / 256, B);
+  hipLaunchKernelGGL(fd_top1_prep_kernel, dim3((unsigned)(((tp.T1 + 7) / 8) * B)), dim3(512), 0, s, evecs_x, ldx, C,
+                     n1, V1max, tp.T1, At, evecs_y, ldy, n2, V2max, (tp.T1 + 7) / 8);
   PK_CHECK_LAUNCH();
-  const dim3 grid((unsigned)((int64_t)B * p.NCG * p.RS)), block(64 * kWaves);
-#define PK_FD_MAIN(K, M)                                                                                          \
-  hipLaunchKernelGGL((fd_main_direct_kernel<K, M>), grid, block, 0, s, A, Bq, nA, nB, n1, n2, p.T1, p.T2, V2max,  \
-                     p.NCG, p.RS, out_idx, out_dist, pv, pi)
-  if (topk == 1) {
-    if (mode == 0) PK_FD_MAIN(1, 0); else if (mode == 1) PK_FD_MAIN(1, 1); else PK_FD_MAIN(1, 2);
+  if (topk == 5) {
+    float* pv = tp.RS > 1 ? reinterpret_cast<float*>(parts) : nullptr;
+    int32_t* pi = tp.RS > 1 ? reinterpret_cast<int32_t*>(parts + tp.t5_bytes) : nullptr;
+    hipLaunchKernelGGL(fd_top5_kernel, grid, dim3(64 * kTop1Waves), 0, s, At, tp.T1, evecs_y, ldy, n1, n2, V2max,
+                       tp.NCG, tp.RS, out_idx, out_dist, pv, pi);
+    PK_CHECK_LAUNCH();
+    if (tp.RS > 1) {
+      hipLaunchKernelGGL(fd_merge_kernel<5>, mg, dim3(256), 0, s, pv, pi, n2, V2max, tp.RS, out_idx, out_dist);
+      PK_CHECK_LAUNCH();
+    }
   } else {
-    if (mode == 0) PK_FD_MAIN(5, 0); else if (mode == 1) PK_FD_MAIN(5, 1); else PK_FD_MAIN(5, 2);
-  }
-#undef PK_FD_MAIN
-  PK_CHECK_LAUNCH();
-  if (p.RS > 1) {
-    const dim3 mg((V2max + 255) / 256, B);
-    if (topk == 1)
-      hipLaunchKernelGGL(fd_merge_kernel<1>, mg, dim3(256), 0, s, pv, pi, n2, V2max, p.RS, out_idx, out_dist);
-    else
-      hipLaunchKernelGGL(fd_merge_kernel<5>, mg, dim3(256), 0, s, pv, pi, n2, V2max, p.RS, out_idx, out_dist);
+    auto* part = reinterpret_cast<unsigned long long*>(parts);
+    hipLaunchKernelGGL(fd_top1_kernel, grid, dim3(64 * kTop1Waves), 0, s, At, tp.T1, evecs_y, ldy, n1, n2, V2max,
+                       tp.NCG, tp.RS, out_idx, out_dist, part);
     PK_CHECK_LAUNCH();
+    if (tp.RS > 1) {
+      hipLaunchKernelGGL(fd_top1_merge_kernel, mg, dim3(256), 0, s, part, n2, V2max, tp.RS, out_idx, out_dist);
+      PK_CHECK_LAUNCH();
+    }
   }
   return PK_OK;
 }

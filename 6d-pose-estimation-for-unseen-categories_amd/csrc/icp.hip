@@ -71,7 +71,7 @@ struct IcpWork {
   double* part;   // [B][nblk][kNPart]
 };
 
-__host__ __device__ inline int64_t al256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+using pk::al256;
 
 __host__ __device__ inline IcpWork carve(void* w, int B, int nsrc_max, int ntgt_max) {
   char* p = static_cast<char*>(w);

@@ -78,21 +78,21 @@ struct RansacWork {
   int64_t* bh;
 };
 
-__host__ __device__ inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+using pk::al256;
 
 __host__ __device__ inline RansacWork carve(void* work, int B, int64_t H, int C, int nhb) {
   char* p = static_cast<char*>(work);
   RansacWork w;
   w.RT = reinterpret_cast<double*>(p);
-  p += align256((int64_t)B * 12 * H * 8);
+  p += al256((int64_t)B * 12 * H * 8);
   w.pe = reinterpret_cast<double*>(p);
-  p += align256((int64_t)B * C * H * 8);
+  p += al256((int64_t)B * C * H * 8);
   w.pg = reinterpret_cast<int32_t*>(p);
-  p += align256((int64_t)B * C * H * 4);
+  p += al256((int64_t)B * C * H * 4);
   w.brmse = reinterpret_cast<double*>(p);
-  p += align256((int64_t)B * nhb * 8);
+  p += al256((int64_t)B * nhb * 8);
   w.bh = reinterpret_cast<int64_t*>(p);
-  p += align256((int64_t)B * nhb * 8);
+  p += al256((int64_t)B * nhb * 8);
   w.bgood = reinterpret_cast<int*>(p);
   return w;
 }
@@ -346,8 +346,8 @@ extern "C" int64_t pk_ransac_work_size(int B, int64_t H, int nmax) {
   if (B <= 0 || H < 0 || nmax < 0) return 0;
   const int C = chunks_for(B, H, nmax);
   const int64_t nhb = (H + kRThreads - 1) / kRThreads;
-  return align256((int64_t)B * 12 * H * 8) + align256((int64_t)B * C * H * 8) + align256((int64_t)B * C * H * 4) +
-         2 * align256((int64_t)B * nhb * 8) + align256((int64_t)B * nhb * 4);
+  return al256((int64_t)B * 12 * H * 8) + al256((int64_t)B * C * H * 8) + al256((int64_t)B * C * H * 4) +
+         2 * al256((int64_t)B * nhb * 8) + al256((int64_t)B * nhb * 4);
 }
 
 extern "C" int pk_ransac(const double* src, const int64_t* src_off, const double* dst, const int64_t* dst_off,

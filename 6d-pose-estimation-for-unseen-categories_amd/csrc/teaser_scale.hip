@@ -599,7 +599,7 @@ struct Layout {
   int ntile_max, nscan_max;
 };
 
-inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+using pk::al256;
 
 Layout layout(int B, int nmax) {
   Layout L;
@@ -610,7 +610,7 @@ Layout layout(int B, int nmax) {
   int64_t o = 0;
   auto take = [&](int64_t bytes) {
     const int64_t at = o;
-    o += align256(bytes);
+    o += al256(bytes);
     return at;
   };
   L.keys0 = take(8 * L.E);

@@ -51,7 +51,7 @@ constexpr int kNNWaves = 4;
 constexpr int kSlab = 64;    // rows of j per projection block
 constexpr int kCP = kKmax + 4;  // LDS row pitch of the staged C (the embed's 64 lanes on 64 distinct banks)
 
-inline int64_t al256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+using pk::al256;
 
 // a crop's valid rows: the caller's count held to [0, the padded length]
 __device__ __forceinline__ int zo_count(int n, int vmax) { return max(0, min(n, vmax)); }

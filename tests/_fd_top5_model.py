@@ -32,7 +32,7 @@ NONE_KEY = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
 def top1_plan(B, V1max, V2max):
-    """(NCG, RS) of a mode-0 top-1 / top-5 launch: top1_plan, csrc/featdist.hip:1373-1387."""
+    """(NCG, RS) of a mode-0 top-1 / top-5 launch: top1_plan in csrc/featdist.hip."""
     T1, T2 = (V1max + 15) // 16, (V2max + 15) // 16
     ncg = max(1, -(-T2 // K_CT))
     blocks = B * ncg
@@ -41,7 +41,8 @@ def top1_plan(B, V1max, V2max):
 
 
 def wave_tiles(n1, RS):
-    """The row-tile range [tb, te) of each of the Q = 8 RS waves (qw = 8 rs + w)."""
+    """The row-tile range [tb, te) of each of the Q = 8 RS waves (qw = 8 rs + w): top1_wave_tiles in
+    csrc/featdist.hip."""
     nt, Q = (n1 + 15) // 16, K_WAVES * RS
     return [(nt * qw // Q, nt * (qw + 1) // Q) for qw in range(Q)]
 

@@ -494,12 +494,13 @@ def test_feat_dist_bf16_configs4_and_ransac(device, coracle, precision):
     assert res.fitness >= 0.5 * agree  # the recovered pose explains the matched points
 
 
-@pytest.mark.parametrize("B,V,ragged", [(4, 1024, False), (32, 256, False), (6, 1024, True)])
+@pytest.mark.parametrize("B,V,ragged", [(4, 1024, False), (32, 256, False), (6, 1024, True), (8, 512, False)])
 def test_feat_dist_top5_exact_vs_emulated_chain(device, B, V, ragged):
     """The round-6 top-5 pass (stream minima + candidate lists + exact recomputation) against the
     host emulation of the same fp32 distances (tests/_util.fd_emulate: the prep's operands and
     the MFMA's fmaf chain) and their stable order: indices, and distances as the sqrt of the
     clamped values. Row parts (B = 4: RS = 4 + the merge launch), one part per block (B = 32 x 256),
+    row parts under the B % 8 == 0 block numbering (B = 8 x 512: NCG 4, RS 2, both merge launches),
     ragged crops with fewer than 5 CAD rows (-1 entries) and empty columns. No column may differ:
     the host's fmaf is exact (tests/_util.fma_f32)."""
     from dpfm_amd import ops

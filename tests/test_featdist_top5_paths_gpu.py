@@ -1,6 +1,7 @@
 """fd_top5_kernel's escape paths on clustered CAD rows (csrc/featdist.hip): the 16-slot candidate
 list and its overflow, E3's ranking, E3b's recompute task list and its overflow, E3c's short list
-and its overflow, the slow path and the row-part merge, against the stable top-5 of the host's
+and its overflow, the slow path and the row-part merge (fd_merge_kernel, csrc/featdist.hpp), against
+the stable top-5 of the host's
 emulation of the same fp32 distances (tests/_util.fd_emulate, exact fmaf). The inputs and the host
 model that shows which path each one takes are in tests/_fd_top5_model.py; tests/
 test_fd_top5_model_cpu.py checks both without a device. Indices must be equal in every column and
